@@ -26,7 +26,24 @@ own JSON line; they are evidence for DESIGN.md, not the driver's line):
              notary: filtered-leaf hashes + partial Merkle tree + multiset check)
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ed25519|ecdsa|tx|backlog|ftx]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what its headline figure needs: it generates and stages the
+workload, runs W warm-up and exactly K timed steps and prints the line (metric,
+value, unit, ms_per_step, config, the timed steps' own kernel spans).  ``--full``
+adds everything else a workload measures or checks, each in runs of its own after
+the timed steps: the verdict checks, the per-kernel times and rooflines, the latency
+and end-to-end records, the PCIe copy rate, the CPU baseline and, for the default
+N = 1 workload, the 32 B tx-id record and the config-3 / config-4 sub-records
+(``--no-cpu-baseline``, ``--no-extra`` and ``--latency-runs`` trim a full run).
+
+``--dump-outputs DIR`` writes what the last timed step handed its caller as
+``DIR/<name>.npy`` (float32, at most 64 MB in all; an output over its share is cut
+to a fixed seeded sample of its elements).  The workloads are seeded, so two runs
+with the same arguments verify identical inputs and two builds can be compared
+output for output.  Where the timed step hands nothing to the host (ed25519,
+ecdsa: verdicts stay in HBM), the last timed step alone also downloads the verdicts.
 
 Multi-GPU: under torchrun (WORLD_SIZE set) every process is one rank and
 WORLD_SIZE must equal --gpus (else exit 2).  Without WORLD_SIZE and --gpus N > 1
@@ -100,15 +117,20 @@ def parse():
                         "tx 131072, backlog 1M per rank)")
     p.add_argument("--msg-bytes", type=int, default=None)
     p.add_argument("--adversarial", type=float, default=0.01)
-    p.add_argument("--latency-runs", type=int, default=21)
-    p.add_argument("--cpu-sample", type=int, default=None, help="units in the CPU-baseline sample")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--latency-runs", type=int, default=21, help="--full: calls per latency figure")
+    p.add_argument("--cpu-sample", type=int, default=None, help="--full: units in the CPU-baseline sample")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--key-reuse", type=int, default=0,
                    help="ed25519/backlog/tx: draw signer keys from this many distinct keys (0 = all distinct)")
     p.add_argument("--no-extra", action="store_true",
-                   help="ed25519 (N=1): skip the 32 B tx-id end-to-end record and the config-3 / config-4 sub-records")
+                   help="--full, ed25519 (N=1): skip the 32 B tx-id end-to-end record and the config-3 / config-4 sub-records")
     p.add_argument("--dry-run", action="store_true",
                    help="launcher / barrier / all-gather logic over gloo on CPU, synthetic step (tests)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the checks, per-kernel times and rooflines, latency / "
+                        "end-to-end records, CPU baseline and (default N = 1 workload) the extra sub-records")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy (float32, <= 64 MB in all)")
     a = p.parse_args()
     a.pool_set = a.pool is not None
     if a.pool is None:
@@ -264,22 +286,45 @@ class Dist:
             self.d.destroy_process_group()
 
 
-def timed(dist, ctx, step, steps, warmup):
+def timed(dist, ctx, step, steps, warmup, last=None):
     """W untimed steps, then exactly K timed steps between barrier+sync pairs;
     returns the max over ranks of the elapsed seconds (kernel stats reset at the
-    start of the timed region, HIP events on the library stream)."""
+    start of the timed region, HIP events on the library stream).  `last`, if given,
+    runs in place of `step` as the K-th timed step (--dump-outputs: the same step,
+    keeping its outputs)."""
     for _ in range(warmup):
         step()
     ctx.set_profiling(True)
     ctx.reset_stats()
     dist.sync()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        step()
+    for i in range(steps):
+        if last is not None and i == steps - 1:
+            last()
+        else:
+            step()
     dist.sync()
     elapsed = time.perf_counter() - t0
     ctx.set_profiling(False)
     return dist.max(elapsed)
+
+
+DUMP_CAP = 64 << 20  # bytes of --dump-outputs, all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> numpy array, any shape or integer
+    dtype) flattened to float32 and saved as <path>/<name>.npy.  The files hold at most
+    DUMP_CAP bytes together: an array over its equal share is cut to a sample of its
+    elements at fixed indices (generator seeded with 0, indices sorted), the same
+    from run to run."""
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_CAP - 4096 * len(arrays)) // max(len(arrays), 1) // 4  # elements; 4 KB spare for each header
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).integers(0, a.size, size=share))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
 
 
 ED_PREP_KERNELS = ("ed25519_hash", "ed25519_points")
@@ -510,6 +555,8 @@ def run_dry(args, dist):
     dist.sync()
     elapsed = dist.max(time.perf_counter() - t0)
     ok = bool(np.array_equal(got[0].numpy(), _dry_words(0, total))) if dist.rank == 0 else None
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, {"accept": np.unpackbits(got[0].numpy().view(np.uint8), bitorder="little")})
     line = base_line(args, dist, "dry-run bitmap all-gathers/sec", "steps/s", args.steps / max(elapsed, 1e-9),
                      elapsed * 1e3 / args.steps, {"workload": "dry run (gloo, CPU)" + (", config-5 shards" if backlog
                                                                                         else ""),
@@ -539,7 +586,7 @@ def run_ed25519(args, dist):
         w = datagen.add_ed25519_adversarial(w, frac=args.adversarial, seed=1 + rank)
     t_gen = time.perf_counter() - t_gen
 
-    tl_path = timeline_path(rank)
+    tl_path = timeline_path(rank) if args.full else None  # (the span log serves the e2e records only)
     ctx = Context(dist.local_rank)
     pb = crypto.PreparedBatch(ctx, crypto.PackedBatch(w.n, w.scheme, w.pk, w.pk_stride, w.sig, w.sig_stride,
                                                       w.sig_len, w.msg, w.msg_off, w.msg_len))
@@ -549,15 +596,36 @@ def run_ed25519(args, dist):
         import torch
         bitmap_dev = torch.zeros(nwords, dtype=torch.int32, device="cuda")
         gathered = torch.zeros(nwords * world, dtype=torch.int32, device="cuda")
+    kept = {}
 
-    def step():
-        pb.verify(MODE_IS_VALID, want_verdicts=False,
-                  device_bitmap_ptr=None if bitmap_dev is None else bitmap_dev.data_ptr())
+    def step(keep=False):
+        v = pb.verify(MODE_IS_VALID, want_verdicts=keep,
+                      device_bitmap_ptr=None if bitmap_dev is None else bitmap_dev.data_ptr())
         if dist.d is not None:
             dist.d.all_gather_into_tensor(gathered, bitmap_dev)  # C1: verdict-bitmap all-gather over RCCL
+        if keep:
+            kept["verdicts"] = v
 
-    elapsed = timed(dist, ctx, step, args.steps, args.warmup)
+    elapsed = timed(dist, ctx, step, args.steps, args.warmup,
+                    last=(lambda: step(True)) if args.dump_outputs else None)
     ks = kstats(ctx, ED_KERNELS + ED_REUSE_KERNELS + ED_AUX_KERNELS)
+    value = n * world * args.steps / elapsed
+    line = base_line(args, dist, "Ed25519 verifies/sec", "verifies/s", value, elapsed * 1e3 / args.steps, {
+        "workload": "BASELINE config 2: EDDSA_ED25519_SHA512 batch verify, "
+                    + (f"keys drawn from {args.key_reuse} signers" if args.key_reuse else
+                       "distinct keys (every 4096th a reference test key, seeds 20..110)")
+                    + f", {msg_bytes} B messages, {args.adversarial:.0%} adversarial (E1-E12)",
+        "batch_per_gpu": n, "global_batch": n * world, "msg_bytes": msg_bytes,
+        "parallelism": f"dp{world} (signature-index shards" + (", RCCL all-gather of accept bitmaps)" if world > 1 else ")")})
+    if args.dump_outputs and rank == 0:
+        if gathered is not None:  # the C1 result: every rank's accept bits, in rank order
+            kept["gathered_accept"] = np.unpackbits(gathered.cpu().numpy().view(np.uint8), bitorder="little")
+        dump_outputs(args.dump_outputs, kept)
+    if not args.full:
+        line.update({"kernels_in_step": ks, "checks": {"datagen_s": round(t_gen, 1)}})
+        pb.close()
+        ctx.close()
+        return line
     # In the timed step the points kernel runs beside the hash kernel (CORDA_AMD_ED_OVERLAP) and a
     # split batch runs as pieces on two streams, so those HIP-event spans overlap: the per-kernel
     # times and the roofline come from 3 extra steps with both off (each kernel alone over the
@@ -634,7 +702,6 @@ def run_ed25519(args, dist):
                     if env is not None:
                         ctx.set_option("CORDA_AMD_ED_PAIR_MAX", None)
 
-    value = n * world * args.steps / elapsed
     model = OP_MODEL["ed25519_1kb" if msg_bytes > 32 else "ed25519_32b"]
     # the key-reuse path runs other kernels under the same timing names (points_r, msm_r),
     # profiled in their own PMC pass (profiles/pmc_ed25519_reuse.json)
@@ -669,13 +736,6 @@ def run_ed25519(args, dist):
         cpu["single_thread"] = {"value": round(one.n / dt1, 1), "cores": 1, "sample": f"first {one.n} signatures",
                                 "verdicts_match_gpu": bool(np.array_equal(cv1, verdict[:one.n]))}
 
-    line = base_line(args, dist, "Ed25519 verifies/sec", "verifies/s", value, elapsed * 1e3 / args.steps, {
-        "workload": "BASELINE config 2: EDDSA_ED25519_SHA512 batch verify, "
-                    + (f"keys drawn from {args.key_reuse} signers" if args.key_reuse else
-                       "distinct keys (every 4096th a reference test key, seeds 20..110)")
-                    + f", {msg_bytes} B messages, {args.adversarial:.0%} adversarial (E1-E12)",
-        "batch_per_gpu": n, "global_batch": n * world, "msg_bytes": msg_bytes,
-        "parallelism": f"dp{world} (signature-index shards" + (", RCCL all-gather of accept bitmaps)" if world > 1 else ")")})
     line.update({
         "roofline": roof,
         "path_roofline": path,
@@ -777,7 +837,7 @@ def config3_subrecord(args, dist, per_curve=1 << 20):
     BC-exact port on a 65,536-signature sample, verdicts compared)."""
     sub = argparse.Namespace(**vars(args))
     sub.batch, sub.msg_bytes, sub.pool_set = per_curve, 1024, False
-    sub.steps, sub.warmup, sub.latency_runs = 5, 2, 3
+    sub.steps, sub.warmup, sub.latency_runs, sub.dump_outputs = 5, 2, 3, None
     sub.no_cpu_baseline, sub.cpu_sample = args.no_cpu_baseline, 65536
     return _subrecord(run_ecdsa(sub, dist), sub)
 
@@ -792,7 +852,7 @@ def config4_subrecord(args, dist, n_tx=1 << 20):
     first-bad indices compared)."""
     sub = argparse.Namespace(**vars(args))
     sub.batch, sub.pool, sub.pool_set, sub.msg_bytes, sub.key_reuse = n_tx, 131072, False, None, 0
-    sub.steps, sub.warmup = 5, 2
+    sub.steps, sub.warmup, sub.dump_outputs = 5, 2, None
     sub.no_cpu_baseline, sub.cpu_sample = args.no_cpu_baseline, 98304
     return _subrecord(run_tx(sub, dist), sub)
 
@@ -839,15 +899,35 @@ def run_ecdsa(args, dist):
         bitmap_dev = torch.zeros(nwords, dtype=torch.int32, device="cuda")
         gathered = torch.zeros(nwords * world, dtype=torch.int32, device="cuda")
 
-    def step():
-        pb.verify(MODE_IS_VALID, want_verdicts=False,
-                  device_bitmap_ptr=None if bitmap_dev is None else bitmap_dev.data_ptr())
+    kept = {}
+
+    def step(keep=False):
+        v = pb.verify(MODE_IS_VALID, want_verdicts=keep,
+                      device_bitmap_ptr=None if bitmap_dev is None else bitmap_dev.data_ptr())
         if dist.d is not None:
             dist.d.all_gather_into_tensor(gathered, bitmap_dev)
+        if keep:
+            kept["verdicts"] = v
 
-    elapsed = timed(dist, ctx, step, args.steps, args.warmup)
+    elapsed = timed(dist, ctx, step, args.steps, args.warmup,
+                    last=(lambda: step(True)) if args.dump_outputs else None)
     names = ["ecdsa_k1_der", "ecdsa_k1_prep", "ecdsa_k1_msm", "ecdsa_r1_der", "ecdsa_r1_prep", "ecdsa_r1_msm"]
     ks_mixed = kstats(ctx, names)
+    value = w.n * world * args.steps / elapsed
+    line = base_line(args, dist, "ECDSA verifies/sec", "verifies/s", value, elapsed * 1e3 / args.steps, {
+        "workload": f"BASELINE config 3: {n} ECDSA_SECP256K1_SHA256 + {n} ECDSA_SECP256R1_SHA256 per GPU, "
+                    f"{msg_bytes} B messages, {args.adversarial:.0%} adversarial (D1-D8); "
+                    + ("distinct keys" if pool == n else f"{pool} distinct signed tuples per curve tiled to size")
+                    + "; every step re-parses the DER signatures (K4) from the device-resident raw rows",
+        "batch_per_gpu": w.n, "global_batch": w.n * world, "msg_bytes": msg_bytes,
+        "parallelism": f"dp{world} (signature-index shards)"})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kept)
+    if not args.full:
+        line.update({"kernels_mixed_step_overlapping": ks_mixed, "checks": {"datagen_s": round(t_gen, 1)}})
+        pb.close()
+        ctx.close()
+        return line
     verdict = pb.verify(MODE_IS_VALID)
     adv = np.array([c != "valid" for c in w.classes])
     untouched_ok = bool((verdict[~adv] == ACCEPT).all())
@@ -872,7 +952,6 @@ def run_ecdsa(args, dist):
         ks.update(kstats(ctx, names))
         cb.close()
 
-    value = w.n * world * args.steps / elapsed
     key = "1kb" if msg_bytes > 32 else "32b"
     ops = {"k1": OP_MODEL["ecdsa_secp256k1"][key], "r1": OP_MODEL["ecdsa_p256"][key]}
     pmc = pmc_view("pmc_ecdsa.json")
@@ -901,13 +980,6 @@ def run_ecdsa(args, dist):
                          f"restatement (oracle/liboracle.so, generic 4x64 Montgomery) on {threads} threads of "
                          f"'{host_cpu_model()}', {dt:.1f} s wall",
                "verdicts_match_gpu": bool(np.array_equal(cv, verdict[idx]))}
-    line = base_line(args, dist, "ECDSA verifies/sec", "verifies/s", value, elapsed * 1e3 / args.steps, {
-        "workload": f"BASELINE config 3: {n} ECDSA_SECP256K1_SHA256 + {n} ECDSA_SECP256R1_SHA256 per GPU, "
-                    f"{msg_bytes} B messages, {args.adversarial:.0%} adversarial (D1-D8); "
-                    + ("distinct keys" if pool == n else f"{pool} distinct signed tuples per curve tiled to size")
-                    + "; every step re-parses the DER signatures (K4) from the device-resident raw rows",
-        "batch_per_gpu": w.n, "global_batch": w.n * world, "msg_bytes": msg_bytes,
-        "parallelism": f"dp{world} (signature-index shards)"})
     line.update({
         "roofline": roof,
         "path_roofline": {"valu_instr_per_verify": round(path_instr) or None,
@@ -972,12 +1044,26 @@ def run_tx(args, dist):
     names = ["merkle_leaf", "merkle_tree", *ED_KERNELS, "ecdsa_k1_prep", "ecdsa_k1_msm",
              "ecdsa_r1_prep", "ecdsa_r1_msm"]
     ks = kstats(ctx, names)
+    value = n_tx * world * args.steps / elapsed
+    line = base_line(args, dist, "SignedTransaction verifies/sec", "tx/s", value, elapsed * 1e3 / args.steps, {
+        "workload": f"BASELINE config 4: {n_tx} SignedTransactions per GPU (trader-demo/loadtest shapes, "
+                    f"{n_sig} signatures, 70/15/15 % Ed25519/R1/K1 over the 32 B id, {args.adversarial:.0%} "
+                    f"tampered); {pool} distinct txs tiled to size; "
+                    + (f"signers drawn from {args.key_reuse} keys per scheme mix; " if args.key_reuse else "")
+                    + "host buffers (page-locked once via cg_register_host) in, per-tx first-bad out",
+        "batch_per_gpu": n_tx, "global_batch": n_tx * world, "parallelism": f"dp{world} (tx-index shards)"})
+    line["signatures_per_s"] = round(n_sig * world * args.steps / elapsed, 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"first_bad": first_bad, "verdicts": verdict, "ids": ids})
+    if not args.full:
+        line.update({"kernels": ks, "checks": {"signatures": n_sig, "datagen_s": round(t_gen, 1)}})
+        ctx.close()
+        return line
     ids_ok = bool(np.array_equal(ids.reshape(-1, 32)[~w.tampered], w.ids.reshape(-1, 32)[~w.tampered]))
     checks = {"untampered_ids_match_signed_ids": ids_ok,
               "tampered_first_bad_is_0": bool((first_bad[w.tampered] == 0).all()),
               "untampered_all_valid": bool((first_bad[~w.tampered] == -1).all()),
               "signatures": n_sig, "datagen_s": round(t_gen, 1)}
-    value = n_tx * world * args.steps / elapsed
     # Merkle kernels: the whole batch's SHA-256 op model over the summed launch time of
     # one step (the batch is hashed in several tx-range chunks, one launch pair each)
     merkle_ms = sum(ks.get(k, {}).get("avg_launch_ms", 0) * ks.get(k, {}).get("launches", 0)
@@ -1020,15 +1106,7 @@ def run_tx(args, dist):
                          f"'{host_cpu_model()}', {dt:.1f} s wall",
                "ids_match_gpu": bool(np.array_equal(cids, ids[:32 * m])),
                "first_bad_match_gpu": bool(np.array_equal(cfb, first_bad[:m]))}
-    line = base_line(args, dist, "SignedTransaction verifies/sec", "tx/s", value, elapsed * 1e3 / args.steps, {
-        "workload": f"BASELINE config 4: {n_tx} SignedTransactions per GPU (trader-demo/loadtest shapes, "
-                    f"{n_sig} signatures, 70/15/15 % Ed25519/R1/K1 over the 32 B id, {args.adversarial:.0%} "
-                    f"tampered); {pool} distinct txs tiled to size; "
-                    + (f"signers drawn from {args.key_reuse} keys per scheme mix; " if args.key_reuse else "")
-                    + "host buffers (page-locked once via cg_register_host) in, per-tx first-bad out",
-        "batch_per_gpu": n_tx, "global_batch": n_tx * world, "parallelism": f"dp{world} (tx-index shards)"})
     line.update({
-        "signatures_per_s": round(n_sig * world * args.steps / elapsed, 1),
         "roofline": {"bound": "pcie", "kernel": "whole step (host buffers in, results out)",
                      "achieved": round(h2d / step_s / 1e9, 2), "peak": pcie, "unit": "GB/s",
                      "frac": round(h2d / step_s / 1e9 / pcie, 4), "traffic": h2d + d2h,
@@ -1071,10 +1149,22 @@ def run_ftx(args, dist):
     elapsed = timed(dist, ctx, step, args.steps, args.warmup)
     ctx.unregister_host(*arrs, out)
     ks = kstats(ctx, ["merkle_leaf", "pmt_eval"])
+    value = n * world * args.steps / elapsed
+    line = base_line(args, dist, "FilteredTransaction verifies/sec", "ftx/s", value, elapsed * 1e3 / args.steps, {
+        "workload": f"SURVEY 8(f) row 1 (non-validating notary): {n} FilteredTransactions per GPU = config-4 "
+                    "transactions filtered to inputs + time window (NotaryFlow.kt:72), partial Merkle tree over "
+                    f"the full tx, {args.adversarial:.0%} adversarial (component / root / tree-hash byte flips); "
+                    "host buffers (page-locked once) in, results out",
+        "batch_per_gpu": n, "global_batch": n * world, "parallelism": f"dp{world} (ftx-index shards)"})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"results": out})
+    if not args.full:
+        line.update({"kernels": ks, "checks": {"datagen_s": round(t_gen, 1)}})
+        ctx.close()
+        return line
     blocks = int(((w.comp_len.astype(np.int64) + 32 + 9 + 63) // 64).sum() + 2 * int((w.node_kind == 2).sum()))
     ops = blocks * OP_MODEL["primitives"]["sha256_block"]
     kms = sum(ks.get(k, {}).get("avg_launch_ms", 0) for k in ("merkle_leaf", "pmt_eval"))
-    value = n * world * args.steps / elapsed
     h2d = len(w.arena) + sum(x.nbytes for x in arrs[1:])
     pcie = pcie_h2d_peak_GBps(dist.local_rank)
     step_s = elapsed / args.steps
@@ -1091,12 +1181,6 @@ def run_ftx(args, dist):
                "sample": f"first {m} filtered txs of the same workload, C restatement (oracle/liboracle.so "
                          f"oracle_ftx_verify_batch, single thread of '{host_cpu_model()}'), {dt:.1f} s wall",
                "results_match_gpu": bool(np.array_equal(cres, out[:m]))}
-    line = base_line(args, dist, "FilteredTransaction verifies/sec", "ftx/s", value, elapsed * 1e3 / args.steps, {
-        "workload": f"SURVEY 8(f) row 1 (non-validating notary): {n} FilteredTransactions per GPU = config-4 "
-                    "transactions filtered to inputs + time window (NotaryFlow.kt:72), partial Merkle tree over "
-                    f"the full tx, {args.adversarial:.0%} adversarial (component / root / tree-hash byte flips); "
-                    "host buffers (page-locked once) in, results out",
-        "batch_per_gpu": n, "global_batch": n * world, "parallelism": f"dp{world} (ftx-index shards)"})
     line.update({
         "roofline": {"bound": "pcie", "kernel": "whole step (host buffers in, results out)",
                      "achieved": round(h2d / step_s / 1e9, 2), "peak": pcie, "unit": "GB/s",
@@ -1148,7 +1232,7 @@ def run_backlog(args, dist):
                 w = datagen.add_ed25519_adversarial(w, frac=args.adversarial, seed=1000 * rank + c0 // chunk)
             pb = crypto.PackedBatch(w.n, w.scheme, w.pk, w.pk_stride, w.sig, w.sig_stride, w.sig_len, w.msg,
                                     w.msg_off, w.msg_len)
-            if c0 == 0:  # verdict spot check on the first chunk; its head is the CPU-baseline sample
+            if c0 == 0 and args.full:  # verdict spot check on the first chunk; its head is the CPU-baseline sample
                 v = crypto.verify_packed(ctx, pb, MODE_IS_VALID)
                 adv = np.array([c != "valid" for c in w.classes])
                 adv_ok[0] = bool((v[~adv] == ACCEPT).all())
@@ -1175,6 +1259,28 @@ def run_backlog(args, dist):
     elapsed = timed(dist, ctx, step, args.steps, args.warmup)
     ks = kstats(ctx, ED_KERNELS + ED_REUSE_KERNELS)
     value = total * args.steps / elapsed
+    line = base_line(args, dist, "Ed25519 verifies/sec (100M notary backlog)", "verifies/s", value,
+                     elapsed * 1e3 / args.steps, {
+                         "workload": f"BASELINE config 5: {total} EDDSA_ED25519_SHA512 signatures over {msg_bytes} B "
+                                     f"tx ids split by index over {world} GPU(s), staged in 2^24 chunks, "
+                                     f"{args.adversarial:.0%} adversarial; {pool} distinct signed tuples per rank "
+                                     "tiled to size" + ("" if args.key_reuse else
+                                                        " (balanced per-signature path forced, "
+                                                        "CORDA_AMD_KEY_REUSE=0: no key dedupe of the tiling)"),
+                         "batch_per_gpu": n, "global_batch": total,
+                         "parallelism": f"dp{world} (index shards" + (", RCCL all-gather)" if world > 1 else ")")},
+                     scaling="strong")
+    if args.dump_outputs and rank == 0:
+        # the step's result is the device accept bitmap: this rank's shard, or after the C1 all-gather the whole backlog
+        words = backlog.bitmap if dist.d is None else ordered
+        dump_outputs(args.dump_outputs, {"accept": np.unpackbits(words.cpu().numpy().view(np.uint8),
+                                                                 bitorder="little")[:n if dist.d is None else total]})
+    if not args.full:
+        line.update({"kernels": ks, "checks": {"datagen_s": round(t_gen, 1), "distinct_tuples_per_rank": pool,
+                                               "stage_s": round(t_stage, 1), "chunks": len(sizes)}})
+        backlog.close()
+        ctx.close()
+        return line
     model = OP_MODEL["ed25519_32b" if msg_bytes <= 32 else "ed25519_1kb"]
     msm = ks.get("ed25519_msm", {})
     reuse = args.key_reuse > 0
@@ -1193,17 +1299,6 @@ def run_backlog(args, dist):
                          f"adversarial elements), C i2p-exact restatement (oracle/liboracle.so) on {threads} threads "
                          f"of '{host_cpu_model()}', {dt:.1f} s wall",
                "verdicts_match_gpu": bool(np.array_equal(cv, first["verdicts"]))}
-    line = base_line(args, dist, "Ed25519 verifies/sec (100M notary backlog)", "verifies/s", value,
-                     elapsed * 1e3 / args.steps, {
-                         "workload": f"BASELINE config 5: {total} EDDSA_ED25519_SHA512 signatures over {msg_bytes} B "
-                                     f"tx ids split by index over {world} GPU(s), staged in 2^24 chunks, "
-                                     f"{args.adversarial:.0%} adversarial; {pool} distinct signed tuples per rank "
-                                     "tiled to size" + ("" if args.key_reuse else
-                                                        " (balanced per-signature path forced, "
-                                                        "CORDA_AMD_KEY_REUSE=0: no key dedupe of the tiling)"),
-                         "batch_per_gpu": n, "global_batch": total,
-                         "parallelism": f"dp{world} (index shards" + (", RCCL all-gather)" if world > 1 else ")")},
-                     scaling="strong")
     line.update({
         "roofline": roof,
         "kernels": ks, "cpu_baseline": cpu,
@@ -1224,9 +1319,9 @@ def main():
     run = run_dry if args.dry_run else {"ed25519": run_ed25519, "ecdsa": run_ecdsa, "tx": run_tx,
                                         "backlog": run_backlog, "ftx": run_ftx}[args.workload]
     line = run(args, dist)
-    if (args.workload == "ed25519" and not args.dry_run and dist.world == 1 and not args.no_extra
+    if (args.full and args.workload == "ed25519" and not args.dry_run and dist.world == 1 and not args.no_extra
             and not args.key_reuse and not args.batch and not args.msg_bytes):
-        # the driver's N = 1 line also carries the production tx-id shape end to end and
+        # the driver's full N = 1 line also carries the production tx-id shape end to end and
         # driver-observed configs 3 and 4 at their BASELINE sizes (each from its own
         # context, after the config-2 timing)
         line["latency_32b"] = e2e_record_32b(args, dist)

@@ -82,6 +82,37 @@ def test_single_rank_dry_run_without_launcher():
     assert json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
 
 
+def test_dump_outputs_dry_run_is_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's result as float32 .npy, the same from
+    run to run; --full is accepted and --steps is the number of timed steps reported."""
+    import numpy as np
+    got = []
+    for d, extra in (("a", []), ("b", ["--full"])):
+        r = _run(["--dry-run", "--steps", "3", "--warmup", "1", "--batch", "1000", "--dump-outputs",
+                  str(tmp_path / d), *extra], _env())
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] >= 0
+        got.append(np.load(tmp_path / d / "accept.npy"))
+    assert got[0].dtype == np.float32 and np.array_equal(got[0], got[1])
+    assert np.array_equal(got[0][:1000], (np.arange(1000) % 7 != 3).astype(np.float32))
+
+
+def test_dump_outputs_stay_under_the_cap(tmp_path, monkeypatch):
+    """An output over its share of the cap is cut to the same seeded sample every time."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_CAP", 1 << 16)
+    big, small = np.arange(100_000, dtype=np.int32), np.arange(10, dtype=np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b) and 0 < len(a) < len(big)
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 1 << 16
+
+
 def test_valu_roofline_fraction_of_peak():
     sys.path.insert(0, ROOT)
     import bench

@@ -42,11 +42,12 @@ run_step() {
       [[ $val == *:* ]] && a=$(args_of "${val#*:}")
       timeout -k 10 600 python -u bench.py $a > "$O/bench_$b.json" 2> "$O/bench_$b.err" ;;
     benchall)
-      run_step "bench=ed25519" && run_step "bench=ed25519_32b:--msg-bytes:32:--no-cpu-baseline" && \
-      run_step "bench=ed25519_reuse64:--key-reuse:64:--no-cpu-baseline" && \
-      run_step "bench=ecdsa:--workload:ecdsa" && run_step "bench=tx:--workload:tx:--steps:5:--warmup:2" && \
-      run_step "bench=ftx:--workload:ftx:--steps:5:--warmup:1" && \
-      run_step "bench=backlog:--workload:backlog:--steps:2:--warmup:1" ;;
+      run_step "bench=ed25519:--full" && run_step "bench=ed25519_32b:--full:--msg-bytes:32:--no-cpu-baseline" && \
+      run_step "bench=ed25519_reuse64:--full:--key-reuse:64:--no-cpu-baseline" && \
+      run_step "bench=ecdsa:--full:--workload:ecdsa" && \
+      run_step "bench=tx:--full:--workload:tx:--steps:5:--warmup:2" && \
+      run_step "bench=ftx:--full:--workload:ftx:--steps:5:--warmup:1" && \
+      run_step "bench=backlog:--full:--workload:backlog:--steps:2:--warmup:1" ;;
     profile)
       local p=${val%%:*} a=
       [[ $val == *:* ]] && a=$(args_of "${val#*:}")
