@@ -33,6 +33,9 @@ TX_OK, TX_NO_SIGNATURES, TX_NO_COMPONENTS, TX_SIGNATURES_MISSING = -1, -2, -3, -
 # cg_set_debug options (test hooks)
 DEBUG_FORCE_FULL_LENGTH, DEBUG_FAIL_ALLOC, DEBUG_THROW, DEBUG_FORCE_GLV_FALLBACK = 1, 2, 3, 4
 ABI_VERSION = 4
+# per-element outcomes of cg_sign_batch, and the elements it processes at a time (CG_SIGN_CHUNK)
+SIGN_OK, SIGN_EMPTY = 0, 1
+SIGN_CHUNK = 1 << 20
 
 # exported symbols and their prototypes: (restype, argtypes)
 _u8p, _u32p, _u64p, _i32p = POINTER(c_uint8), POINTER(c_uint32), POINTER(c_uint64), POINTER(ctypes.c_int32)
@@ -71,6 +74,12 @@ PROTOTYPES = {
     "cg_reset_stats": (c_int, [c_void_p]),
     "cg_set_debug": (c_int, [c_void_p, c_int, ctypes.c_int64]),
     "cg_set_option": (c_int, [c_void_p, c_char_p, c_char_p]),
+    "cg_signer_create": (c_int, [c_void_p, c_size_t, c_void_p, POINTER(c_void_p)]),
+    "cg_signer_size": (c_size_t, [c_void_p]),
+    "cg_signer_public_keys": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "cg_signer_destroy": (None, [c_void_p, c_void_p]),
+    "cg_sign_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                              c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -254,3 +254,128 @@ class PreparedBatch:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------- signing
+# ``Crypto.doSign(privateKey, clearData)`` (Crypto.kt:394-401) for EDDSA_ED25519_SHA512
+# keys, batched: what a notary does to every transaction id it accepts
+# (NotaryFlow.kt:125-126 -> NotaryService.kt:75-77 -> keyManagementService.sign).  i2p's
+# EdDSAEngine signs deterministically (RFC 8032), so the 64 bytes equal the JVM's.  ECDSA
+# signing stays on the JVM: BC 1.57 draws its nonce from SecureRandom.
+SIGN_OK, SIGN_EMPTY = _lib.SIGN_OK, _lib.SIGN_EMPTY
+
+
+class SigningException(Exception):
+    """What ``Crypto.doSign`` throws for an element (Crypto.kt:397: empty clear data), or a
+    signature that failed its verify-after-sign check."""
+
+    def __init__(self, msg: str, index: int | None = None):
+        super().__init__(msg)
+        self.index = index
+
+
+def entropy_to_seed(k: int) -> bytes:
+    """The Ed25519 seed of Corda's ``entropyToKeyPair(BigInteger.valueOf(k))``
+    (Crypto.kt:733-739): ``BigInteger.toByteArray()`` (big-endian, minimal two's
+    complement) then ``copyOf(32)`` (cut or zero-padded on the right to 32 bytes)."""
+    raw = int(k).to_bytes((int(k).bit_length() + 8) // 8, "big", signed=True)
+    return (raw + bytes(32))[:32]
+
+
+class Ed25519Signer:
+    """Private keys held on the device (``cg_signer_create``).  ``seeds``: one 32-byte seed
+    per key, the wire form of an ``EdDSAPrivateKey`` (Kryo.kt:316-320)."""
+
+    def __init__(self, ctx: _lib.Context, seeds: Sequence[bytes]):
+        seeds = [bytes(s) for s in seeds]
+        if any(len(s) != 32 for s in seeds):
+            raise IllegalArgumentException("an Ed25519 seed is 32 bytes")
+        self.ctx, self.n_keys, self.h = ctx, len(seeds), None
+        buf = np.frombuffer(b"".join(seeds) or bytes(32), dtype=np.uint8).copy()
+        h = _lib.c_void_p()
+        try:
+            ctx.check(ctx.lib.cg_signer_create(ctx.h, self.n_keys, _lib.ptr(buf), _lib.ctypes.byref(h)))
+        finally:
+            buf[:] = 0  # this module's own copy of the seeds
+        self.h = h
+        self._pk = None
+
+    @property
+    def public_keys(self) -> list[bytes]:
+        if self._pk is None:
+            out = np.zeros((max(self.n_keys, 1), 32), dtype=np.uint8)
+            self.ctx.check(self.ctx.lib.cg_signer_public_keys(self.ctx.h, self.h, _lib.ptr(out)))
+            self._pk = [out[j].tobytes() for j in range(self.n_keys)]
+        return list(self._pk)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.ctx.h:  # (a closed context has already released the device arrays)
+                self.ctx.lib.cg_signer_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sign_packed(ctx: _lib.Context, signer: Ed25519Signer, msg: np.ndarray, msg_off: np.ndarray, msg_len: np.ndarray,
+                key_index: np.ndarray | None = None):
+    """``cg_sign_batch`` on arrays in the C ABI's layout (the message arena of
+    ``PackedBatch``); returns (signatures [n, 64] uint8, status [n] uint8)."""
+    n = len(msg_len)
+    msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+    msg_len = np.ascontiguousarray(msg_len, dtype=np.uint32)
+    if key_index is not None:
+        key_index = np.ascontiguousarray(key_index, dtype=np.uint32)
+        if len(key_index) != n:
+            raise IllegalArgumentException("key_index and clear_data differ in length")
+    if len(msg_off) != n:
+        raise IllegalArgumentException("msg_off and msg_len differ in length")
+    sig = np.zeros((max(n, 1), 64), dtype=np.uint8)
+    status = np.zeros(max(n, 1), dtype=np.uint8)
+    ctx.check(ctx.lib.cg_sign_batch(ctx.h, signer.h, n, _lib.ptr(key_index), _lib.ptr(msg), len(msg),
+                                    _lib.ptr(msg_off), _lib.ptr(msg_len), _lib.ptr(sig), _lib.ptr(status)))
+    return sig[:n], status[:n]
+
+
+def sign_batch(ctx: _lib.Context, signer: Ed25519Signer, clear_data: Sequence[bytes], key_index=None):
+    """Signs clear_data[i] with key key_index[i] of the signer (None: key 0 throughout).
+    Returns (signatures [n, 64] uint8, status [n]): SIGN_OK, or SIGN_EMPTY with a zero row
+    for empty clear data."""
+    n = len(clear_data)
+    msg_len = np.array([len(m) for m in clear_data], dtype=np.uint32)
+    msg_off = np.zeros(n, dtype=np.uint64)
+    if n:
+        msg_off[1:] = np.cumsum(msg_len[:-1], dtype=np.uint64)
+    arena = np.frombuffer(b"".join(bytes(m) for m in clear_data) or b"\0", dtype=np.uint8).copy()
+    return sign_packed(ctx, signer, arena, msg_off, msg_len, key_index)
+
+
+def do_sign_batch(ctx: _lib.Context, signer: Ed25519Signer, clear_data: Sequence[bytes], key_index=None,
+                  verify_after_sign: bool = False) -> list[bytes]:
+    """``for i in range(n): Crypto.doSign(key[key_index[i]], clear_data[i])``: the n
+    signatures, or the exception of the lowest failing index.  verify_after_sign: every
+    signature is verified on the device before any is returned, the usual guard against a
+    faulted computation leaking the key."""
+    sig, status = sign_batch(ctx, signer, clear_data, key_index)
+    bad = np.flatnonzero(status != SIGN_OK)
+    if bad.size:
+        raise SigningException("Signing of an empty array is not permitted!", int(bad[0]))
+    sigs = [sig[i].tobytes() for i in range(len(clear_data))]
+    if verify_after_sign and sigs:
+        pks = signer.public_keys
+        idx = np.zeros(len(sigs), dtype=np.int64) if key_index is None else np.asarray(key_index, dtype=np.int64)
+        v = is_valid_batch(ctx, EDDSA_ED25519_SHA512, [pks[int(j)] for j in idx], sigs, clear_data)
+        wrong = np.flatnonzero(v != ACCEPT)
+        if wrong.size:
+            raise SigningException("signature failed verification after signing", int(wrong[0]))
+    return sigs

@@ -79,6 +79,28 @@ hipError_t launch_ed25519_points_lanes(const Ed25519Dev& d, uint32_t n, uint32_t
 hipError_t launch_ed25519_msm_lanes(const Ed25519Dev& d, uint32_t n, uint32_t lanes, const uint32_t* out_index,
                                     uint8_t* verdict, hipStream_t s);
 
+// Ed25519 signing (K9).  keyexp: 32-byte seed rows -> the signer's SoA arrays a (mod L),
+// prefix, abyte ([8][n_keys] words each).  sign: element i of the view signs
+// arena[msg_off[i] .. + msg_len[i]) with key key_index[i] (null: key 0; every index
+// < n_keys) -> sig[16 i ..] (64 bytes, R then S) and status[i] (0 ok, 1 empty message:
+// zero row, the arena is not read).
+struct Ed25519SignDev {
+  const uint32_t* key_index = nullptr;
+  const uint32_t* a = nullptr;
+  const uint32_t* prefix = nullptr;
+  const uint32_t* abyte = nullptr;
+  uint32_t n_keys = 0;
+  const uint8_t* arena = nullptr;
+  const uint64_t* msg_off = nullptr;
+  const uint32_t* msg_len = nullptr;
+  const int32_t* btab = nullptr;
+  uint32_t* sig = nullptr;
+  uint8_t* status = nullptr;
+};
+hipError_t launch_ed25519_keyexp(const uint32_t* seeds, uint32_t n_keys, const int32_t* btab, uint32_t* a,
+                                 uint32_t* prefix, uint32_t* abyte, hipStream_t s);
+hipError_t launch_ed25519_sign(const Ed25519SignDev& d, uint32_t n, hipStream_t s);
+
 // Staging: element-major host layout -> SoA words.  `idx` (optional) gathers a
 // per-scheme subset.  Byte-granular so any stride works.
 hipError_t launch_gather_words(const uint8_t* src, size_t stride, size_t offset, uint32_t nwords,

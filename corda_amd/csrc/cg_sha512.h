@@ -227,4 +227,68 @@ CG_HD void sha512_ed25519(uint32_t out[16], const uint32_t r[8], const uint32_t 
   }
 }
 
+// SHA-512(prefix || M) for a register-held prefix of PW little-endian u32 words, PW = 0,
+// 8 or 16 (0, 32 or 64 bytes), M = msg[0..n): the block loader of sha512_ed25519 with the
+// prefix length as a parameter (PW = 16 with prefix = R || Abyte gives sha512_ed25519's
+// digest).  The signing path uses PW = 8: the nonce hash SHA-512(prefix || M), and the
+// key expansion SHA-512(seed) as a 32-byte prefix with an empty message.  n = 0 reads
+// nothing through msg (it may be null); otherwise the reader's bounds are
+// sha512_ed25519's.  Output: the digest as 16 little-endian u32 words.
+template <int PW>
+CG_HD void sha512_prefixed(uint32_t out[16], const uint32_t* prefix, const uint8_t* msg, uint32_t n) {
+  static_assert(PW == 0 || PW == 8 || PW == 16, "prefix of 0, 32 or 64 bytes");
+  constexpr int PB = 4 * PW;  // prefix bytes
+  uint64_t h[8], w[16];
+  sha512_init(h);
+  const uintptr_t addr = (uintptr_t)msg;
+  const uint32_t* m4 = (const uint32_t*)(addr & ~(uintptr_t)3);
+  const uint32_t sh = (uint32_t)(addr & 3);
+  const uint64_t total = PB + (uint64_t)n;
+  const uint32_t nb = (uint32_t)((total + 17 + 127) / 128);
+  const int64_t ndw = n ? ((int64_t)n + sh + 3) >> 2 : 0;  // dwords that hold message bytes
+  CG_NOUNROLL for (uint32_t blk = 0; blk < nb; ++blk) {
+    const int64_t q0 = 128 * (int64_t)blk - PB;  // message byte offset of word 0
+    if (PW != 0 && blk == 0 && (int64_t)n >= 128 - PB && 2 * (16 - PW / 2) < ndw) {
+      // the prefix words, then whole message words with the dword after them readable
+      CG_UNROLL for (int j = 0; j < PW / 2; ++j) w[j] = be64_from_le32(prefix[2 * j], prefix[2 * j + 1]);
+      sha512_load_words<16 - PW / 2>(w + PW / 2, m4, sh);
+    } else if (q0 >= 0 && q0 + 128 <= (int64_t)n && (q0 >> 2) + 32 < ndw) {
+      sha512_load_words<16>(w, m4 + (q0 >> 2), sh);
+    } else {
+      CG_UNROLL for (int j = 0; j < 16; ++j) {
+        const int64_t off = 128 * (int64_t)blk + 8 * j;  // stream byte offset
+        uint64_t word;
+        if (off < PB) {
+          word = be64_from_le32(prefix[2 * j], prefix[2 * j + 1]);  // (blk = 0 here)
+        } else {
+          const int64_t q = off - PB;  // message byte offset (multiple of 8)
+          const int64_t c = (int64_t)n - q;
+          if (c <= 0) {
+            word = (c == 0) ? (0x80ULL << 56) : 0;
+          } else {
+            const int64_t d0 = q >> 2;
+            const uint32_t x0 = ld32(m4, d0);
+            const uint32_t x1 = (d0 + 1 < ndw) ? ld32(m4, d0 + 1) : 0u;
+            const uint32_t x2 = (d0 + 2 < ndw) ? ld32(m4, d0 + 2) : 0u;
+            word = be64_from_le32(alignbyte(x1, x0, sh), alignbyte(x2, x1, sh));
+            if (c < 8) {
+              const int keep = (int)c * 8;
+              word &= ~((~0ULL) >> keep);      // zero bytes >= n
+              word |= 0x80ULL << (56 - keep);  // padding marker at byte n
+            }
+          }
+        }
+        if (blk == nb - 1 && j == 14) word = 0;
+        if (blk == nb - 1 && j == 15) word = total * 8;
+        w[j] = word;
+      }
+    }
+    sha512_block(h, w);
+  }
+  CG_UNROLL for (int i = 0; i < 8; ++i) {
+    out[2 * i] = bswap32((uint32_t)(h[i] >> 32));
+    out[2 * i + 1] = bswap32((uint32_t)h[i]);
+  }
+}
+
 }  // namespace cg

@@ -3396,3 +3396,188 @@ cg_status cg_composite_eval_batch(cg_ctx* ctx, size_t n_q, const uint32_t* prog_
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- Ed25519 signing (K9)
+// Device-resident signer: the expanded private keys, SoA over the keys ([8][n_keys] words
+// each; ed25519_kernels.hip).  a and prefix are secret; all three arrays are zeroed before
+// their blocks go back to the context's cache.
+struct cg_signer {
+  size_t n_keys = 0;
+  uint32_t* a = nullptr;       // a mod L
+  uint32_t* prefix = nullptr;  // h[32..63] of SHA-512(seed)
+  uint32_t* abyte = nullptr;   // enc([a]B)
+};
+
+namespace {
+
+// Zeroes a device block that held key material, waits for the fill, then returns the
+// block to the cache (dfree alone would hand the bytes to the next allocation).
+void wipe_free(cg_ctx* ctx, void* p, size_t bytes) {
+  if (!p) return;
+  (void)hipMemsetAsync(p, 0, bytes, ctx->stream);
+  (void)hipStreamSynchronize(ctx->stream);
+  dfree(ctx, p);
+}
+
+void signer_free(cg_ctx* ctx, cg_signer* s) {
+  if (!s) return;
+  const size_t bytes = 8 * s->n_keys * sizeof(uint32_t);
+  wipe_free(ctx, s->a, bytes);
+  wipe_free(ctx, s->prefix, bytes);
+  wipe_free(ctx, s->abyte, bytes);
+  delete s;
+}
+
+}  // namespace
+
+extern "C" {
+
+cg_status cg_signer_create(cg_ctx* ctx, size_t n_keys, const uint8_t* seeds, cg_signer** out) {
+  CG_API_BEGIN
+  if (!ctx) return CG_E_INVALID_ARGUMENT;
+  if (!out) return fail(ctx, CG_E_INVALID_ARGUMENT, "null signer output");
+  *out = nullptr;
+  if (n_keys && !seeds) return fail(ctx, CG_E_INVALID_ARGUMENT, "null seeds");
+  if (n_keys > 0xFFFFFFF0ull) return fail(ctx, CG_E_INVALID_ARGUMENT, "more than 2^32 - 16 keys");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, CG_E_DEVICE, "hipSetDevice");
+  cg_signer* s = new (std::nothrow) cg_signer();
+  if (!s) return fail(ctx, CG_E_OUT_OF_MEMORY, "host allocation failed");
+  s->n_keys = n_keys;
+  if (n_keys == 0) {  // nothing to expand, nothing to launch
+    *out = s;
+    return CG_OK;
+  }
+  // The seeds go up straight from the caller's buffer: the library makes no host staging
+  // copy of them, so there is none to wipe; the device copy is zeroed below.
+  uint8_t* seeds_d = nullptr;
+  const size_t seed_bytes = 32 * n_keys;
+  cg_status st;
+  if ((st = dalloc(ctx, &seeds_d, seed_bytes, "alloc seeds")) == CG_OK &&
+      (st = dalloc(ctx, &s->a, 8 * n_keys, "alloc signer scalars")) == CG_OK &&
+      (st = dalloc(ctx, &s->prefix, 8 * n_keys, "alloc signer prefixes")) == CG_OK &&
+      (st = dalloc(ctx, &s->abyte, 8 * n_keys, "alloc signer public keys")) == CG_OK) {
+    hipError_t e = hipMemcpyAsync(seeds_d, seeds, seed_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+      Timed t(ctx, "ed25519_keyexp", n_keys);
+      e = cg::launch_ed25519_keyexp(reinterpret_cast<const uint32_t*>(seeds_d), (uint32_t)n_keys, ctx->btab, s->a,
+                                    s->prefix, s->abyte, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) st = hip_fail(ctx, e, "ed25519 key expansion");
+  }
+  wipe_free(ctx, seeds_d, seed_bytes);
+  collect_timings(ctx);
+  if (st != CG_OK) {
+    signer_free(ctx, s);
+    return st;
+  }
+  *out = s;
+  return CG_OK;
+  CG_API_END(ctx)
+}
+
+size_t cg_signer_size(const cg_signer* s) { return s ? s->n_keys : 0; }
+
+cg_status cg_signer_public_keys(cg_ctx* ctx, const cg_signer* s, uint8_t* pk_out) {
+  CG_API_BEGIN
+  if (!ctx) return CG_E_INVALID_ARGUMENT;
+  if (!s) return fail(ctx, CG_E_INVALID_ARGUMENT, "null signer");
+  if (s->n_keys == 0) return CG_OK;
+  if (!pk_out) return fail(ctx, CG_E_INVALID_ARGUMENT, "null pk_out");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, CG_E_DEVICE, "hipSetDevice");
+  std::vector<uint32_t> w(8 * s->n_keys);  // word-major on the device; rows for the caller
+  CG_TRY(ctx, hipMemcpyAsync(w.data(), s->abyte, w.size() * 4, hipMemcpyDeviceToHost, ctx->stream),
+         "download public keys");
+  CG_TRY(ctx, hipStreamSynchronize(ctx->stream), "download public keys");
+  for (size_t j = 0; j < s->n_keys; ++j)
+    for (int k = 0; k < 8; ++k) std::memcpy(pk_out + 32 * j + 4 * k, &w[(size_t)k * s->n_keys + j], 4);
+  return CG_OK;
+  CG_API_END(ctx)
+}
+
+void cg_signer_destroy(cg_ctx* ctx, cg_signer* s) {
+  try {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    signer_free(ctx, s);
+  } catch (...) {
+    api_guard_fail(ctx);
+  }
+}
+
+cg_status cg_sign_batch(cg_ctx* ctx, const cg_signer* s, size_t n, const uint32_t* key_index, const uint8_t* msg,
+                        size_t msg_bytes, const uint64_t* msg_off, const uint32_t* msg_len, uint8_t* sig_out,
+                        uint8_t* status_out) {
+  CG_API_BEGIN
+  if (!ctx) return CG_E_INVALID_ARGUMENT;
+  if (!s) return fail(ctx, CG_E_INVALID_ARGUMENT, "null signer");
+  if (n == 0) return CG_OK;
+  if (n > 0xFFFFFFF0ull) return fail(ctx, CG_E_INVALID_ARGUMENT, "batch larger than 2^32 - 16 elements");
+  if (!sig_out || !msg_off || !msg_len || (msg_bytes > 0 && !msg))
+    return fail(ctx, CG_E_INVALID_ARGUMENT, "null input pointer");
+  if (s->n_keys == 0) return fail(ctx, CG_E_INVALID_ARGUMENT, "the signer holds no keys");
+  for (size_t i = 0; key_index && i < n; ++i)
+    if (key_index[i] >= s->n_keys)
+      return fail(ctx, CG_E_INVALID_ARGUMENT, "key_index out of range at element " + std::to_string(i));
+  {
+    const size_t i = first_out_of_arena(msg_off, msg_len, n, msg_bytes);
+    if (i < n) return fail(ctx, CG_E_INVALID_ARGUMENT, out_of_arena_message(i));
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, CG_E_DEVICE, "hipSetDevice");
+  // the whole arena once (+ the readers' 16-byte pad), then CG_SIGN_CHUNK elements at a
+  // time through one set of per-chunk buffers (stream order keeps a chunk's kernel and
+  // downloads ahead of the next chunk's uploads).  r and a live in registers only: no
+  // per-call scratch holds secrets.
+  const size_t cap = std::min<size_t>(n, CG_SIGN_CHUNK);
+  uint8_t *arena_d = nullptr, *stat_d = nullptr;
+  uint64_t* off_d = nullptr;
+  uint32_t *len_d = nullptr, *idx_d = nullptr, *sig_d = nullptr;
+  cg_status st;
+  if ((st = dalloc(ctx, &arena_d, msg_bytes + 16, "alloc arena")) == CG_OK &&
+      (st = dalloc(ctx, &off_d, cap, "alloc msg_off")) == CG_OK &&
+      (st = dalloc(ctx, &len_d, cap, "alloc msg_len")) == CG_OK &&
+      (!key_index || (st = dalloc(ctx, &idx_d, cap, "alloc key_index")) == CG_OK) &&
+      (st = dalloc(ctx, &sig_d, 16 * cap, "alloc signatures")) == CG_OK &&
+      (st = dalloc(ctx, &stat_d, cap, "alloc sign status")) == CG_OK) {
+    hipError_t e = hipSuccess;
+    if (msg_bytes) e = hipMemcpyAsync(arena_d, msg, msg_bytes, hipMemcpyHostToDevice, ctx->stream);
+    cg::Ed25519SignDev d;
+    d.key_index = idx_d;
+    d.a = s->a;
+    d.prefix = s->prefix;
+    d.abyte = s->abyte;
+    d.n_keys = (uint32_t)s->n_keys;
+    d.arena = arena_d;
+    d.msg_off = off_d;
+    d.msg_len = len_d;
+    d.btab = ctx->btab;
+    d.sig = sig_d;
+    d.status = stat_d;
+    for (size_t base = 0; base < n && e == hipSuccess; base += cap) {
+      const size_t m = std::min(cap, n - base);
+      e = hipMemcpyAsync(off_d, msg_off + base, m * 8, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(len_d, msg_len + base, m * 4, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess && key_index)
+        e = hipMemcpyAsync(idx_d, key_index + base, m * 4, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess) {
+        Timed t(ctx, "ed25519_sign", m);
+        e = cg::launch_ed25519_sign(d, (uint32_t)m, ctx->stream);
+      }
+      if (e == hipSuccess) e = hipMemcpyAsync(sig_out + 64 * base, sig_d, 64 * m, hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess && status_out)
+        e = hipMemcpyAsync(status_out + base, stat_d, m, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) st = hip_fail(ctx, e, "ed25519 sign");
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  for (const void* p : {(const void*)arena_d, (const void*)off_d, (const void*)len_d, (const void*)idx_d,
+                        (const void*)sig_d, (const void*)stat_d})
+    dfree(ctx, p);
+  collect_timings(ctx);
+  return st;
+  CG_API_END(ctx)
+}
+
+}  // extern "C"

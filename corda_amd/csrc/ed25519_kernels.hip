@@ -12,6 +12,14 @@
 //                       tables B and 2^128 B in HBM), identity test -> verdict
 //   cg_ed25519_btab_build  the shared tables (context creation)
 //
+// K9: Ed25519 batch signing (cg_ed25519_sign.h), one lane per element:
+//
+//   cg_ed25519_keyexp   seed -> a mod L, prefix, Abyte = enc([a]B), once per signer key
+//                       (profiling span "ed25519_keyexp")
+//   cg_ed25519_sign     nonce hash, R = enc([r]B) over the shared tables, challenge hash,
+//                       S = (r + k a) mod L -> 64 signature bytes and a status byte
+//                       (profiling span "ed25519_sign")
+//
 // Integer VALU work only (no MFMA): field products are v_mad_i64_i32.
 // Device layout (SoA, word-major, `cap` = batch capacity, i = element):
 //   pk[w*cap+i] (8 words), sig[w*cap+i] (16 words: R then S), sig_len[i],
@@ -24,6 +32,7 @@
 //   quad-major layout across lanes — each wave load one contiguous 1 KB run — slower:
 //   msm 7.11 -> 8.35 ms, points 2.47 -> 3.9 ms per 1 M, an entry's quads 16 MB apart.)
 #include "cg_ed25519.h"
+#include "cg_ed25519_sign.h"
 #include "cg_kernels.h"
 
 using namespace cg;
@@ -630,6 +639,59 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CG_MSM_R_WA
   verdict[dst] = ok ? (uint8_t)V_ACCEPT : (uint8_t)V_REJECT;
 }
 
+// ---------------------------------------------------------------- K9: signing
+// Signer arrays (SoA, word-major over the signer's n_keys keys): a[w * n_keys + j],
+// prefix[...], abyte[...] (8 words each).  Signatures leave as rows: word w of element i
+// at sig[16 i + w] (the host layout, R then S), status[i] = SIGN_OK / SIGN_EMPTY.
+// Occupancy target (waves per SIMD) of the signing kernels: the point phase's live set
+// is the MSM's (two waves).
+#ifndef CG_SIGN_WAVES
+#define CG_SIGN_WAVES 2
+#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CG_SIGN_WAVES, 8))) void cg_ed25519_keyexp(
+    const uint32_t* __restrict__ seeds, uint32_t n_keys, const int32_t* __restrict__ btab_g, uint32_t* __restrict__ a_out,
+    uint32_t* __restrict__ prefix_out, uint32_t* __restrict__ abyte_out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_keys) return;
+  uint32_t seed[8], a[8], prefix[8], ab[8];
+  CG_UNROLL for (int w = 0; w < 8; ++w) seed[w] = seeds[(size_t)8 * j + w];  // 32-byte rows as given
+  ed25519_expand_seed(a, prefix, seed);
+  ed25519_public_key(ab, a, [&](uint32_t t, uint32_t k, ge_precomp& p) CG_LINLINE { load_bentry(btab_g, t, k, p); });
+  CG_UNROLL for (int w = 0; w < 8; ++w) {
+    a_out[(size_t)w * n_keys + j] = a[w];
+    prefix_out[(size_t)w * n_keys + j] = prefix[w];
+    abyte_out[(size_t)w * n_keys + j] = ab[w];
+  }
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CG_SIGN_WAVES, 8))) void cg_ed25519_sign(
+    const uint32_t* __restrict__ key_index, const uint32_t* __restrict__ a_g, const uint32_t* __restrict__ prefix_g,
+    const uint32_t* __restrict__ abyte_g, uint32_t n_keys, const uint8_t* __restrict__ arena,
+    const uint64_t* __restrict__ msg_off, const uint32_t* __restrict__ msg_len, uint32_t n,
+    const int32_t* __restrict__ btab_g, uint32_t* __restrict__ sig, uint8_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int4* row = reinterpret_cast<int4*>(sig + (size_t)16 * i);
+  const uint32_t len = msg_len[i];
+  if (len == 0) {  // Crypto.kt:397: never reads the arena
+    CG_UNROLL for (int q = 0; q < 4; ++q) row[q] = make_int4(0, 0, 0, 0);
+    status[i] = (uint8_t)SIGN_EMPTY;
+    return;
+  }
+  const uint32_t j = key_index ? key_index[i] : 0u;  // (< n_keys: checked on the host before the launch)
+  uint32_t a[8], prefix[8], ab[8], s[16];
+  CG_UNROLL for (int w = 0; w < 8; ++w) {
+    a[w] = a_g[(size_t)w * n_keys + j];
+    prefix[w] = prefix_g[(size_t)w * n_keys + j];
+    ab[w] = abyte_g[(size_t)w * n_keys + j];
+  }
+  ed25519_sign_stage(s, a, prefix, ab, arena + msg_off[i], len,
+                     [&](uint32_t t, uint32_t k, ge_precomp& p) CG_LINLINE { load_bentry(btab_g, t, k, p); });
+  CG_UNROLL for (int q = 0; q < 4; ++q)
+    row[q] = make_int4((int)s[4 * q], (int)s[4 * q + 1], (int)s[4 * q + 2], (int)s[4 * q + 3]);
+  status[i] = (uint8_t)SIGN_OK;
+}
+
 }  // namespace
 
 namespace cg {
@@ -754,6 +816,21 @@ hipError_t launch_ed25519_bucket(const Ed25519Dev& d, uint32_t n, const uint32_t
                      out_index, verdict);
   hipLaunchKernelGGL(cg_ed25519_bucket_scatter, grid, dim3(kBucketBlock), 0, s, d.status, d.pstat, n, d.scap,
                      d.order_count, d.order);
+  return hipGetLastError();
+}
+
+hipError_t launch_ed25519_keyexp(const uint32_t* seeds, uint32_t n_keys, const int32_t* btab, uint32_t* a,
+                                 uint32_t* prefix, uint32_t* abyte, hipStream_t s) {
+  if (n_keys == 0) return hipSuccess;
+  hipLaunchKernelGGL(cg_ed25519_keyexp, dim3((n_keys + 255) / 256), dim3(256), 0, s, seeds, n_keys, btab, a, prefix,
+                     abyte);
+  return hipGetLastError();
+}
+
+hipError_t launch_ed25519_sign(const Ed25519SignDev& d, uint32_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(cg_ed25519_sign, dim3((n + 255) / 256), dim3(256), 0, s, d.key_index, d.a, d.prefix, d.abyte,
+                     d.n_keys, d.arena, d.msg_off, d.msg_len, n, d.btab, d.sig, d.status);
   return hipGetLastError();
 }
 

@@ -73,6 +73,8 @@
 extern "C" {
 #endif
 
+/* The signing entry points (cg_signer_*, cg_sign_batch) are purely additive: no existing
+ * signature or layout changed, so the version stays 4. */
 #define CG_ABI_VERSION 4  /* 4: cg_set_option; the CORDA_AMD_* knobs read once, at cg_open */
 
 typedef int32_t cg_status;
@@ -274,6 +276,46 @@ enum { CG_COMPOSITE_LEAF = 0, CG_COMPOSITE_NODE = 1, CG_COMPOSITE_INVALID = 0x80
 cg_status cg_composite_eval_batch(cg_ctx* ctx, size_t n_q, const uint32_t* prog_start, const int32_t* prog,
                                   size_t n_sig, const uint32_t* sig_start, const uint8_t* verdicts, uint8_t* out);
 /*
+ * Ed25519 batch signing (EDDSA_ED25519_SHA512, the default scheme): a loop of
+ * Crypto.doSign(privateKey, clearData), core/.../crypto/Crypto.kt:394-401 (i2p
+ * EdDSAEngine.sign: deterministic, RFC 8032) — what a notary does to every transaction id
+ * it accepts: NotaryFlow.kt:125-126 service.sign(txId.bytes) -> NotaryService.kt:75-77
+ * keyManagementService.sign -> Crypto.doSign.  The 64 signature bytes equal the JVM's.
+ * ECDSA signing is not offered: BC 1.57 draws its nonce from SecureRandom, so there is no
+ * byte-exact target.
+ *
+ * A cg_signer holds n_keys private keys on the device, expanded once.  seeds: 32 bytes per
+ * key, the wire form of an EdDSAPrivateKey (Ed25519PrivateKeySerializer writes obj.seed,
+ * Kryo.kt:316-320).  The library keeps no host copy of the seeds; the device arrays that
+ * hold key material are zeroed before their memory is reused.  cg_last_error never
+ * contains key or nonce bytes.  Table lookups on the device are indexed by secret digits
+ * (not constant-time): run one notary process per GPU.
+ * cg_signer_public_keys: the keys' public halves A, 32 bytes each (EdDSAPublicKey.abyte).
+ *
+ * cg_sign_batch: element i signs msg[msg_off[i] .. msg_off[i] + msg_len[i]) (the arena
+ * layout of cg_verify_batch) with key key_index[i] (NULL: every element uses key 0).
+ * sig_out: n * 64 bytes, R || S per element.  status_out (optional, n bytes):
+ *   CG_SIGN_OK     signed
+ *   CG_SIGN_EMPTY  empty clear data: doSign throws IllegalArgumentException("Signing of an
+ *                  empty array is not permitted!", Crypto.kt:397); the element's 64
+ *                  signature bytes are zero.  A per-element outcome: the call returns CG_OK.
+ * A key_index[i] >= n_keys or a message outside the arena returns CG_E_INVALID_ARGUMENT
+ * before anything is launched (the message names the element).  Batches larger than
+ * CG_SIGN_CHUNK elements are processed CG_SIGN_CHUNK elements at a time.
+ * Profiling spans: "ed25519_keyexp" (cg_signer_create), "ed25519_sign" (cg_sign_batch).
+ */
+typedef struct cg_signer cg_signer;
+enum { CG_SIGN_OK = 0, CG_SIGN_EMPTY = 1 };
+#define CG_SIGN_CHUNK (1u << 20)
+cg_status cg_signer_create(cg_ctx* ctx, size_t n_keys, const uint8_t* seeds, cg_signer** out);
+size_t cg_signer_size(const cg_signer* signer);
+cg_status cg_signer_public_keys(cg_ctx* ctx, const cg_signer* signer, uint8_t* pk_out);
+void cg_signer_destroy(cg_ctx* ctx, cg_signer* signer);
+cg_status cg_sign_batch(cg_ctx* ctx, const cg_signer* signer, size_t n, const uint32_t* key_index,
+                        const uint8_t* msg, size_t msg_bytes, const uint64_t* msg_off, const uint32_t* msg_len,
+                        uint8_t* sig_out, uint8_t* status_out);
+
+/*
  * Host-memory registration (optional).  Page-locks [ptr, ptr + bytes) for the
  * device so later uploads from that range run at full PCIe DMA rate instead of
  * through the runtime's pageable staging copy.  Meant for buffers a caller reuses
@@ -290,7 +332,8 @@ cg_status cg_release_cached(cg_ctx* ctx);
  * Per-kernel device timing (HIP events on the context's stream), accumulated while
  * profiling is enabled.  Names: "ed25519_hash", "ed25519_points", "ed25519_msm",
  * "ecdsa_k1_prep", "ecdsa_k1_msm", "ecdsa_r1_prep", "ecdsa_r1_msm", "der_parse",
- * "merkle_leaf", "merkle_tree", "pmt_eval", "composite_eval", "stage".
+ * "merkle_leaf", "merkle_tree", "pmt_eval", "composite_eval", "stage", "ed25519_keyexp",
+ * "ed25519_sign".
  * enable: 0 off, 1 every span, 2 only the "call" span of each cg_verify_batch (its
  * GPU time from entry to the verdict download; two events per call).
  */

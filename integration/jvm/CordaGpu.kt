@@ -21,6 +21,8 @@ import java.security.InvalidKeyException
 import java.security.PublicKey
 import java.security.SignatureException
 import java.security.interfaces.ECPublicKey
+import net.corda.core.crypto.SecureHash
+import net.i2p.crypto.eddsa.EdDSAPrivateKey
 import net.i2p.crypto.eddsa.EdDSAPublicKey
 
 /** Verdict codes of cg_verify_batch (include/cordagpu.h). */
@@ -106,12 +108,71 @@ class CordaGpu(device: Int = 0) : AutoCloseable {
         return Pair(codes, miss)
     }
 
+    /**
+     * Ed25519 private keys expanded once on the device (cg_signer_create).  A key goes over as its
+     * 32-byte seed, the form Ed25519PrivateKeySerializer writes (Kryo.kt:316-320); the direct buffer
+     * that carried the seeds is zeroed before the constructor returns.
+     */
+    inner class Signer(privateKeys: List<EdDSAPrivateKey>) : AutoCloseable {
+        val n = privateKeys.size
+        private val s: Long
+        init {
+            val seeds = direct(32 * n)
+            privateKeys.forEach { seeds.put(it.seed) }
+            try {
+                s = nativeSignerCreate(handle, n, seeds)
+            } finally {
+                for (i in 0 until 32 * n) seeds.put(i, 0)
+            }
+            check(s > 0L) { "libcordagpu error $s: ${nativeLastError(handle)}" }
+        }
+
+        /** A (EdDSAPublicKey.abyte) of every key, as the device derived it. */
+        fun publicKeys(): List<ByteArray> {
+            val out = direct(32 * n)
+            check(nativeSignerPublicKeys(handle, s, out))
+            return (0 until n).map { j -> ByteArray(32).also { out.position(32 * j); out.get(it) } }
+        }
+
+        /**
+         * A loop of [Crypto.doSign] (Crypto.kt:394-401) in one device call: clearData[i] signed with key
+         * keyIndex[i] (null: key 0).  Throws what the loop would throw first: IllegalArgumentException
+         * for the lowest empty element (Crypto.kt:397).
+         */
+        fun sign(clearData: List<ByteArray>, keyIndex: IntArray? = null): List<ByteArray> {
+            val m = clearData.size
+            val msg = direct(clearData.sumBy { it.size }); val msgOff = direct(8 * m); val msgLen = direct(4 * m)
+            val idx = keyIndex?.let { k -> direct(4 * m).also { b -> k.forEachIndexed { i, v -> b.putInt(4 * i, v) } } }
+            var off = 0L
+            for (i in 0 until m) {
+                msgOff.putLong(8 * i, off); msgLen.putInt(4 * i, clearData[i].size)
+                msg.position(off.toInt()); msg.put(clearData[i]); off += clearData[i].size
+            }
+            val sig = direct(64 * m); val status = direct(m)
+            check(signBatch(handle, s, m, idx, msg, msgOff, msgLen, sig, status))
+            for (i in 0 until m)
+                require(status.get(i).toInt() == SIGN_OK) { "Signing of an empty array is not permitted!" }
+            return (0 until m).map { i -> ByteArray(64).also { sig.position(64 * i); sig.get(it) } }
+        }
+
+        override fun close() = nativeSignerDestroy(handle, s)
+    }
+
+    /** Batch form of [Crypto.doSign]: element i signed with privateKeys[i] (Ed25519 keys only). */
+    fun doSignBatch(privateKeys: List<EdDSAPrivateKey>, clearData: List<ByteArray>): List<ByteArray> {
+        require(privateKeys.size == clearData.size) { "privateKeys and clearData differ in length" }
+        val distinct = privateKeys.distinct()
+        val slot = distinct.withIndex().associate { (j, k) -> k to j }
+        return Signer(distinct).use { it.sign(clearData, IntArray(clearData.size) { i -> slot[privateKeys[i]]!! }) }
+    }
+
     class PackedBatch(val n: Int, val scheme: ByteBuffer, val pk: ByteBuffer, val sig: ByteBuffer, val sigStride: Int,
                       val sigLen: ByteBuffer, val msg: ByteBuffer, val msgOff: ByteBuffer, val msgLen: ByteBuffer)
 
     companion object {
         const val PK_STRIDE = 64
         const val CG_E_MERKLE_EMPTY = -5
+        const val SIGN_OK = 0; const val SIGN_EMPTY = 1  // cg_sign_batch status bytes
         init { System.loadLibrary("cordagpu_jni") }
 
         @JvmStatic external fun nativeOpen(device: Int): Long
@@ -144,6 +205,12 @@ class CordaGpu(device: Int = 0) : AutoCloseable {
                                                 compLen: ByteBuffer, compStart: ByteBuffer, nonces: ByteBuffer,
                                                 nodeStart: ByteBuffer, nodeKind: ByteBuffer, nodeHash: ByteBuffer,
                                                 roots: ByteBuffer, result: ByteBuffer): Int
+        @JvmStatic external fun nativeSignerCreate(handle: Long, nKeys: Int, seeds: ByteBuffer): Long
+        @JvmStatic external fun nativeSignerPublicKeys(handle: Long, signer: Long, pkOut: ByteBuffer): Int
+        @JvmStatic external fun nativeSignerDestroy(handle: Long, signer: Long)
+        @JvmStatic external fun signBatch(handle: Long, signer: Long, n: Int, keyIndex: ByteBuffer?, msg: ByteBuffer,
+                                          msgOff: ByteBuffer, msgLen: ByteBuffer, sigOut: ByteBuffer,
+                                          status: ByteBuffer?): Int
         @JvmStatic external fun nativeCompositeEval(handle: Long, nQ: Int, progStart: ByteBuffer, prog: ByteBuffer,
                                                     nSig: Int, sigStart: ByteBuffer, verdicts: ByteBuffer?,
                                                     out: ByteBuffer): Int
@@ -377,4 +444,27 @@ fun verifySignaturesExceptBatch(stxs: List<SignedTransaction>, allowed: List<Set
                 missing[j].toSet().let { net.corda.core.utilities.NonEmptySet.copyOf(it) }, batch[j].getKeyDescriptions(missing[j].toSet()), batch[j].id)
         else -> batch[j].verifySignaturesExcept(*allowed[dev[j]].toTypedArray())  // NO_SIGNATURES / NO_COMPONENTS: the JVM throws
     }
+}
+
+// ---------------------------------------------------------------- signing (Crypto.doSign, Crypto.kt:394-401)
+/** `privateKeys.indices.map { Crypto.doSign(privateKeys[it], clearData[it]) }` for Ed25519 keys, one device call. */
+fun Crypto.doSignBatch(gpu: CordaGpu, privateKeys: List<EdDSAPrivateKey>, clearData: List<ByteArray>): List<ByteArray> =
+        gpu.doSignBatch(privateKeys, clearData)
+
+/**
+ * Sketch of the notary's reply path, batched: NotaryFlow.kt:125-126 calls `service.sign(txId.bytes)` per
+ * accepted transaction, which NotaryService.kt:75-77 forwards to `keyManagementService.sign(bits, notaryKey)`
+ * and that to Crypto.doSign.  A notary that drains its backlog in batches keeps one [CordaGpu.Signer] for its
+ * identity key (the key management service hands the private key to the signer once, at start-up) and signs
+ * every accepted id of a batch in one call; each result is wrapped exactly as `sign` wraps it.
+ */
+class NotaryBatchSigner(gpu: CordaGpu, notaryPrivateKey: EdDSAPrivateKey, private val notaryIdentityKey: PublicKey)
+    : AutoCloseable {
+    private val signer = gpu.Signer(listOf(notaryPrivateKey))
+
+    /** `txIds.map { service.sign(it.bytes) }` */
+    fun signBatch(txIds: List<SecureHash>): List<DigitalSignature.WithKey> =
+            signer.sign(txIds.map { it.bytes }).map { DigitalSignature.WithKey(notaryIdentityKey, it) }
+
+    override fun close() = signer.close()
 }

@@ -8,6 +8,9 @@
  *   nativeFtxVerify         cg_ftx_verify_batch      FilteredTransaction.verify (MerkleTransaction.kt:173-178)
  *   nativeCompositeEval     cg_composite_eval_batch  isFulfilledBy / CompositeSignature (CompositeKey.kt:186-209)
  *   nativeSetOption         cg_set_option            a context's CORDA_AMD_* tuning knobs
+ *   nativeSignerCreate/...  cg_signer_*              Ed25519 private keys expanded once on the device
+ *   signBatch               cg_sign_batch            a loop of Crypto.doSign (Crypto.kt:394-401): the notary's
+ *                                                    service.sign(txId.bytes) (NotaryFlow.kt:125-126)
  *
  * Build on a JVM host against the JDK's jni.h:
  *   gcc -O2 -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include \
@@ -120,4 +123,45 @@ JNIEXPORT jint JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_nativeCompositeEv
     jobject verdicts, jobject out) {
   return cg_composite_eval_batch(CTX(h), (size_t)n_q, BUF(prog_start), BUF(prog), (size_t)n_sig, BUF(sig_start),
                                  BUF(verdicts), BUF(out));
+}
+
+/* Signing (cg_signer_*, cg_sign_batch: Crypto.doSign, Crypto.kt:394-401).  The signer handle
+ * is a cg_signer* as a jlong (a failed create returns the negative cg_status); seeds: a
+ * direct buffer of 32 bytes per key, which the caller overwrites after the call. */
+JNIEXPORT jlong JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_nativeSignerCreate(JNIEnv* env, jclass cls, jlong h,
+                                                                                   jint n_keys, jobject seeds) {
+  cg_signer* s = 0;
+  if (n_keys < 0 || CAP(seeds) < (size_t)n_keys * 32) return CG_E_INVALID_ARGUMENT;
+  const cg_status st = cg_signer_create(h > 0 ? CTX(h) : 0, (size_t)n_keys, BUF(seeds), &s);
+  return st == CG_OK ? (jlong)(intptr_t)s : (jlong)st;
+}
+
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_nativeSignerPublicKeys(JNIEnv* env, jclass cls,
+                                                                                      jlong h, jlong signer,
+                                                                                      jobject pk_out) {
+  if (signer <= 0) return CG_E_INVALID_ARGUMENT;
+  const cg_signer* s = (const cg_signer*)(intptr_t)signer;
+  if (CAP(pk_out) < cg_signer_size(s) * 32) return CG_E_INVALID_ARGUMENT;
+  return cg_signer_public_keys(h > 0 ? CTX(h) : 0, s, BUF(pk_out));
+}
+
+JNIEXPORT void JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_nativeSignerDestroy(JNIEnv* env, jclass cls, jlong h,
+                                                                                   jlong signer) {
+  if (h > 0 && signer > 0) cg_signer_destroy(CTX(h), (cg_signer*)(intptr_t)signer);
+}
+
+/* One call per batch: key_index (null: key 0), the message arena with its offsets and
+ * lengths, sig_out (n * 64 bytes) and status (null, or n bytes) are direct buffers. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_signBatch(JNIEnv* env, jclass cls, jlong h,
+                                                                         jlong signer, jint n, jobject key_index,
+                                                                         jobject msg, jobject msg_off,
+                                                                         jobject msg_len, jobject sig_out,
+                                                                         jobject status) {
+  if (signer <= 0 || n < 0) return CG_E_INVALID_ARGUMENT;
+  const size_t m = (size_t)n;
+  if ((key_index && CAP(key_index) < 4 * m) || CAP(msg_off) < 8 * m || CAP(msg_len) < 4 * m ||
+      CAP(sig_out) < 64 * m || (status && CAP(status) < m))
+    return CG_E_INVALID_ARGUMENT;
+  return cg_sign_batch(h > 0 ? CTX(h) : 0, (const cg_signer*)(intptr_t)signer, m, BUF(key_index), BUF(msg), CAP(msg),
+                       BUF(msg_off), BUF(msg_len), BUF(sig_out), BUF(status));
 }
