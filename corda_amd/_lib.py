@@ -64,6 +64,10 @@ PROTOTYPES = {
                                                c_void_p, c_void_p]),
     "cg_ftx_verify_batch": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cg_ftx_build_layout": (c_int, [c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cg_ftx_build_batch": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
     "cg_composite_eval_batch": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                         c_void_p]),
     "cg_register_host": (c_int, [c_void_p, c_void_p, c_size_t]),

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cg_pmt_build.h"
+
 namespace cg {
 
 // All pointers are device pointers (layout: merkle_kernels.hip).
@@ -29,7 +31,7 @@ hipError_t launch_first_bad(const uint8_t* verdict, const uint32_t* sig_start, u
 
 // Partial Merkle tree verdicts (status codes below); stack: 8 * max_depth * n words.
 enum : uint8_t { kPmtTrue = 0, kPmtFalse = 1, kPmtNoLeaves = 2, kPmtMalformed = 3, kPmtHostCheck = 4 };
-enum : uint8_t { kPmtIncluded = 0, kPmtLeaf = 1, kPmtNode = 2 };
+// (node kinds kPmtIncluded / kPmtLeaf / kPmtNode: cg_pmt_build.h)
 constexpr uint32_t kPmtMaxLane = 256;
 // Node-program well-formedness (status) and per-wave deepest stack (depth_w[(n + 63) / 64]).
 hipError_t launch_pmt_scan(const uint32_t* node_start, const uint8_t* node_kind, uint32_t n, uint8_t* status,
@@ -37,5 +39,22 @@ hipError_t launch_pmt_scan(const uint32_t* node_start, const uint8_t* node_kind,
 hipError_t launch_pmt_eval(const uint32_t* node_start, const uint8_t* node_kind, const uint32_t* node_hash,
                            const uint32_t* comp_start, const uint32_t* leaves, const uint32_t* roots, uint32_t n,
                            uint32_t* stack, uint8_t* status, hipStream_t s);
+
+// Partial Merkle tree construction (cg_ftx_build_batch; per-tx logic: cg_pmt_build.h).
+// nonces[8 j ..] (digest byte order) = SHA256(salt_t || BE32(i)) of filtered component j =
+// component fcomp_index[j] (< n_comp), the i-th of tx t = comp_tx[..].
+hipError_t launch_pmt_nonce(const uint32_t* fcomp_index, uint32_t n_fcomp, uint32_t n_comp,
+                            const uint32_t* comp_start, const uint32_t* comp_tx, const uint32_t* salts,
+                            uint32_t* nonces, hipStream_t s);
+// One lane per tx of [0, n) (comp_start / node_start / roots already offset to the first):
+// the tx's post-order program into node_kind / node_hash at node_start[t] .., its root into
+// roots[8 t ..] (zero for a tx without components).  leaves: K5's output, read only.
+// inc_prefix[c] = number of included components before component c (n_comp + 1 entries).
+// park: 8 * max(levels, 1) * stride words, stride >= n; levels >= the deepest tx's
+// pmt_levels (a deeper tx is skipped: its nodes stay as they were).
+hipError_t launch_pmt_build(const uint32_t* leaves, const uint32_t* comp_start, const uint32_t* inc_prefix,
+                            const uint32_t* node_start, uint32_t n, uint32_t levels, uint32_t stride,
+                            uint32_t* park, uint8_t* node_kind, uint32_t* node_hash, uint32_t* roots,
+                            hipStream_t s);
 
 }  // namespace cg

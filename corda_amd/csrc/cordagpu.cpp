@@ -37,6 +37,7 @@
 
 #include "cg_composite_api.h"
 #include "cg_ecdsa_api.h"
+#include "cg_ftx_layout.h"
 #include "cg_kernels.h"
 #include "cg_merkle_api.h"
 #include "cg_plan.h"
@@ -3305,6 +3306,152 @@ cg_status cg_ftx_verify_batch(cg_ctx* ctx, size_t n_ftx, const uint8_t* arena, s
     if (e) (void)hipEventDestroy(e);
   d.release(ctx);
   collect_timings(ctx);
+  return st;
+  CG_API_END(ctx)
+}
+
+}  // extern "C"
+
+namespace {
+
+using cg::FtxBuildLayout;
+
+// Device buffers of cg_ftx_build_batch beyond the tx-id ones.
+struct FtxBuildDev {
+  TxDev d;
+  uint32_t *inc_prefix = nullptr, *node_start = nullptr, *fcomp_index = nullptr, *nonces = nullptr, *node_hash = nullptr,
+           *park = nullptr;
+  uint8_t* node_kind = nullptr;
+  void release(cg_ctx* ctx) {
+    for (const void* p : {(const void*)inc_prefix, (const void*)node_start, (const void*)fcomp_index,
+                          (const void*)nonces, (const void*)node_hash, (const void*)park, (const void*)node_kind})
+      dfree(ctx, p);
+    d.release(ctx);
+  }
+};
+
+// Everything on ctx->stream: uploads, K5 (leaf hashes, as cg_txid_batch runs it), the
+// nonces of the filtered components, then the tree pass over tx-index chunks that share
+// one set of parked-hash slots (8 words per level and lane; stream order keeps a chunk's
+// kernel ahead of the next one's), and the downloads.  CORDA_AMD_FTX_BUILD_CHUNK
+// overrides the chunk's tx count.
+cg_status ftx_build_run(cg_ctx* ctx, size_t n_tx, const uint8_t* arena, size_t arena_bytes, const uint64_t* comp_off,
+                        const uint32_t* comp_len, const uint32_t* comp_start, const uint8_t* salts,
+                        const FtxBuildLayout& lay, const uint32_t* fcomp_index, uint8_t* nonces_out,
+                        uint8_t* node_kind_out, uint8_t* node_hash_out, uint8_t* root_out, FtxBuildDev& b) {
+  const size_t n_comp = comp_start[n_tx], n_f = lay.fstart[n_tx], n_n = lay.nstart[n_tx];
+  bool any_empty = false;
+  cg_status st = compute_txids(ctx, n_tx, arena, arena_bytes, comp_off, comp_len, comp_start, salts, nullptr, b.d,
+                               &any_empty, /*upload_arena=*/false);
+  if (st != CG_OK) return st;
+  size_t chunk = 262144;
+  if (ctx->opts.has(cg::OPT_FTX_BUILD_CHUNK)) chunk = (size_t)std::max(1, ctx->opts.i(cg::OPT_FTX_BUILD_CHUNK, 262144));
+  chunk = std::min(chunk, n_tx);
+  const uint32_t levels = cg::pmt_levels(lay.max_k);
+  if ((st = upload(ctx, &b.inc_prefix, lay.inc_prefix.data(), n_comp + 1, "upload include prefix")) != CG_OK ||
+      (st = upload(ctx, &b.node_start, lay.nstart.data(), n_tx + 1, "upload node_start")) != CG_OK ||
+      (st = upload(ctx, &b.fcomp_index, fcomp_index, n_f, "upload filtered component index")) != CG_OK ||
+      (st = dalloc(ctx, &b.nonces, 8 * n_f, "alloc nonces")) != CG_OK ||
+      (st = dalloc(ctx, &b.node_kind, n_n, "alloc node_kind")) != CG_OK ||
+      (st = dalloc(ctx, &b.node_hash, 8 * n_n, "alloc node_hash")) != CG_OK ||
+      (st = dalloc(ctx, &b.park, (size_t)8 * std::max(levels, 1u) * chunk, "alloc parked hashes")) != CG_OK)
+    return st;
+  if (arena_bytes)
+    CG_TRY(ctx, hipMemcpyAsync(b.d.arena, arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream), "upload tx arena");
+  if (n_n) CG_TRY(ctx, hipMemsetAsync(b.node_kind, 0xff, n_n, ctx->stream), "fill node_kind");
+  {
+    Timed t(ctx, "merkle_leaf", n_comp - comp_start[0]);
+    CG_TRY(ctx, cg::launch_merkle_leaf(b.d.arena, arena_bytes, b.d.comp_off, b.d.comp_len, b.d.comp_start, b.d.comp_tx,
+                                       b.d.salts, nullptr, comp_start[0], (uint32_t)n_comp, b.d.leaves, ctx->err_flag,
+                                       ctx->stream, b.d.order + comp_start[0], b.d.leaf_hist),
+           "launch merkle_leaf");
+  }
+  {
+    Timed t(ctx, "pmt_nonce", n_f);
+    CG_TRY(ctx, cg::launch_pmt_nonce(b.fcomp_index, (uint32_t)n_f, (uint32_t)n_comp, b.d.comp_start, b.d.comp_tx,
+                                     b.d.salts, b.nonces, ctx->stream),
+           "launch pmt_nonce");
+  }
+  for (size_t t0 = 0; t0 < n_tx; t0 += chunk) {
+    const size_t nk = std::min(chunk, n_tx - t0);
+    Timed t(ctx, "pmt_build", nk);
+    CG_TRY(ctx, cg::launch_pmt_build(b.d.leaves, b.d.comp_start + t0, b.inc_prefix, b.node_start + t0, (uint32_t)nk,
+                                     levels, (uint32_t)chunk, b.park, b.node_kind, b.node_hash,
+                                     (uint32_t*)b.d.ids + 8 * t0, ctx->stream),
+           "launch pmt_build");
+  }
+  if (n_f) CG_TRY(ctx, hipMemcpyAsync(nonces_out, b.nonces, 32 * n_f, hipMemcpyDeviceToHost, ctx->stream), "download nonces");
+  if (n_n) {
+    CG_TRY(ctx, hipMemcpyAsync(node_kind_out, b.node_kind, n_n, hipMemcpyDeviceToHost, ctx->stream), "download node_kind");
+    CG_TRY(ctx, hipMemcpyAsync(node_hash_out, b.node_hash, 32 * n_n, hipMemcpyDeviceToHost, ctx->stream),
+           "download node_hash");
+  }
+  CG_TRY(ctx, hipMemcpyAsync(root_out, b.d.ids, 32 * n_tx, hipMemcpyDeviceToHost, ctx->stream), "download roots");
+  return read_err_flag(ctx);
+}
+
+}  // namespace
+
+extern "C" {
+
+cg_status cg_ftx_build_layout(size_t n_tx, const uint32_t* comp_start, const uint8_t* include,
+                              uint32_t* fcomp_start_out, uint32_t* node_start_out) {
+  try {
+    if (!fcomp_start_out || !node_start_out) return CG_E_INVALID_ARGUMENT;
+    FtxBuildLayout lay;
+    std::string err;
+    if (!cg::ftx_build_layout(n_tx, comp_start, include, lay, err)) return CG_E_INVALID_ARGUMENT;
+    std::copy(lay.fstart.begin(), lay.fstart.end(), fcomp_start_out);
+    std::copy(lay.nstart.begin(), lay.nstart.end(), node_start_out);
+    return CG_OK;
+  } catch (const std::bad_alloc&) {
+    return CG_E_OUT_OF_MEMORY;
+  } catch (...) {
+    return CG_E_INVALID_ARGUMENT;
+  }
+}
+
+cg_status cg_ftx_build_batch(cg_ctx* ctx, size_t n_tx, const uint8_t* arena, size_t arena_bytes,
+                             const uint64_t* comp_off, const uint32_t* comp_len, const uint32_t* comp_start,
+                             const uint8_t* salts, const uint8_t* include, size_t fcomp_cap, size_t node_cap,
+                             uint32_t* fcomp_start_out, uint32_t* fcomp_index_out, uint8_t* nonces_out,
+                             uint32_t* node_start_out, uint8_t* node_kind_out, uint8_t* node_hash_out,
+                             uint8_t* root_out) {
+  CG_API_BEGIN
+  if (!ctx) return CG_E_INVALID_ARGUMENT;
+  if (n_tx == 0) return CG_OK;
+  if (!comp_start || !salts || !fcomp_start_out || !node_start_out || !root_out)
+    return fail(ctx, CG_E_INVALID_ARGUMENT, "null pointer");
+  FtxBuildLayout lay;
+  std::string err;
+  if (!cg::ftx_build_layout(n_tx, comp_start, include, lay, err)) return fail(ctx, CG_E_INVALID_ARGUMENT, err);
+  cg_status st;
+  const size_t c_begin = comp_start[0], n_comp = comp_start[n_tx], n_f = lay.fstart[n_tx], n_n = lay.nstart[n_tx];
+  if (n_comp > c_begin && (!comp_off || !comp_len || !arena)) return fail(ctx, CG_E_INVALID_ARGUMENT, "null pointer");
+  if (n_f > fcomp_cap || n_n > node_cap)
+    return fail(ctx, CG_E_INVALID_ARGUMENT,
+                "output capacity too small: the batch needs " + std::to_string(n_f) + " filtered components and " +
+                    std::to_string(n_n) + " nodes");
+  if ((n_f && (!fcomp_index_out || !nonces_out)) || (n_n && (!node_kind_out || !node_hash_out)))
+    return fail(ctx, CG_E_INVALID_ARGUMENT, "null pointer");
+  if (n_comp > c_begin) {
+    const size_t i = first_out_of_arena(comp_off + c_begin, comp_len + c_begin, n_comp - c_begin, arena_bytes);
+    if (i < n_comp - c_begin)
+      return fail(ctx, CG_E_INVALID_ARGUMENT, "component " + std::to_string(c_begin + i) + " out of arena bounds");
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, CG_E_DEVICE, "hipSetDevice");
+  std::copy(lay.fstart.begin(), lay.fstart.end(), fcomp_start_out);
+  std::copy(lay.nstart.begin(), lay.nstart.end(), node_start_out);
+  for (size_t c = c_begin; c < n_comp; ++c)
+    if (lay.inc_prefix[c + 1] != lay.inc_prefix[c]) fcomp_index_out[lay.inc_prefix[c]] = (uint32_t)c;
+  FtxBuildDev b;
+  st = ftx_build_run(ctx, n_tx, arena, arena_bytes, comp_off, comp_len, comp_start, salts, lay, fcomp_index_out,
+                     nonces_out, node_kind_out, node_hash_out, root_out, b);
+  (void)hipStreamSynchronize(ctx->stream);
+  b.release(ctx);
+  collect_timings(ctx);
+  if (st == CG_OK && lay.any_empty)
+    return fail(ctx, CG_E_MERKLE_EMPTY, "Cannot calculate Merkle root on empty hash list.");
   return st;
   CG_API_END(ctx)
 }

@@ -19,6 +19,10 @@
 //                    HBM scratch, root compare, multiset check of the included
 //                    leaves against the filtered components' hashes
 //                    (PartialMerkleTree.kt:130-155, MerkleTransaction.kt:173-178)
+//   k_pmt_nonce      one lane per filtered component: its nonce, for FilteredLeaves.nonces
+//   cg_pmt_build     one lane per tx: the full tree over K5's leaves in one depth-first
+//                    pass (cg_pmt_build.h) that writes the partial tree's post-order
+//                    program and the root (PartialMerkleTree.kt:66-123)
 #include "cg_kernels.h"
 #include "cg_merkle_api.h"
 #include "cg_sha256.h"
@@ -309,6 +313,92 @@ __global__ __launch_bounds__(256) void cg_pmt_eval(const uint32_t* __restrict__ 
   status[t] = ok ? kPmtTrue : kPmtFalse;
 }
 
+// Nonces of the filtered components (FilteredLeaves.nonces): K5 keeps a component's nonce
+// in registers only, so the few included ones are hashed again here (one compression
+// each; no leaf hash is recomputed).  One lane per filtered component.
+__global__ __launch_bounds__(256) void k_pmt_nonce(const uint32_t* __restrict__ fcomp_index, uint32_t n_fcomp,
+                                                   uint32_t n_comp, const uint32_t* __restrict__ comp_start,
+                                                   const uint32_t* __restrict__ comp_tx,
+                                                   const uint32_t* __restrict__ salts,
+                                                   uint32_t* __restrict__ nonces) {
+  CG_WAVE_PRIO(2);
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_fcomp) return;
+  const uint32_t c = fcomp_index[j];
+  if (c >= n_comp) return;
+  const uint32_t t = comp_tx[c];
+  uint32_t m[9], h[8];
+  CG_UNROLL for (int w = 0; w < 8; ++w) m[w] = bswap32_(salts[(size_t)t * 8 + w]);
+  m[8] = c - comp_start[t];  // ByteBuffer.putInt: big-endian
+  sha256_words<36>(h, m);
+  CG_UNROLL for (int w = 0; w < 8; ++w) nonces[(size_t)j * 8 + w] = bswap32_(h[w]);
+}
+
+// The sink of cg_pmt_build.h's pass on the device: the running hash in registers, the
+// parked left children (one per level) in an HBM slot per lane — word q of level l of lane
+// t at park[(8 l + q) stride + t], coalesced across the wave like cg_pmt_eval's stack (a
+// 32-level array of 8-word hashes indexed by a run-time level would otherwise go to
+// scratch memory).
+struct PmtBuildSink {
+  const uint32_t* leaves;  // the tx's leaf hashes (8 big-endian-valued words each)
+  uint32_t k;
+  uint32_t* park;          // + lane
+  size_t stride;
+  uint8_t* kind_out;
+  uint32_t* hash_out;
+  uint32_t pos, end;       // next program position, one past the tx's last
+  uint32_t cur[8];
+  CG_HDM void leaf(uint64_t i) {
+    CG_UNROLL for (int q = 0; q < 8; ++q) cur[q] = i < k ? leaves[(size_t)i * 8 + q] : 0u;
+  }
+  CG_HDM void emit(int kind) {
+    if (pos < end) {
+      kind_out[pos] = (uint8_t)kind;
+      CG_UNROLL for (int q = 0; q < 8; ++q)
+        hash_out[(size_t)pos * 8 + q] = kind == kPmtNode ? 0u : bswap32_(cur[q]);  // digest byte order
+    }
+    ++pos;
+  }
+  CG_HDM void combine(uint32_t l) {
+    uint32_t m[16];
+    CG_UNROLL for (int q = 0; q < 8; ++q) {
+      m[q] = park[((size_t)8 * l + q) * stride];
+      m[8 + q] = cur[q];
+    }
+    sha256_words<64>(cur, m);  // SecureHash.hashConcat (SecureHash.kt:25)
+  }
+  CG_HDM void park_hash(uint32_t l) {
+    CG_UNROLL for (int q = 0; q < 8; ++q) park[((size_t)8 * l + q) * stride] = cur[q];
+  }
+};
+
+__global__ __launch_bounds__(256) void cg_pmt_build(const uint32_t* __restrict__ leaves,
+                                                    const uint32_t* __restrict__ comp_start,
+                                                    const uint32_t* __restrict__ inc_prefix,
+                                                    const uint32_t* __restrict__ node_start, uint32_t n,
+                                                    uint32_t levels, uint32_t stride, uint32_t* __restrict__ park,
+                                                    uint8_t* __restrict__ node_kind,
+                                                    uint32_t* __restrict__ node_hash, uint32_t* __restrict__ roots) {
+  CG_WAVE_PRIO(2);
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const uint32_t c0 = comp_start[t], k = comp_start[t + 1] - c0;
+  PmtBuildSink s;
+  s.leaves = leaves + (size_t)c0 * 8;
+  s.k = k;
+  s.park = park + t;
+  s.stride = stride;
+  s.kind_out = node_kind;
+  s.hash_out = node_hash;
+  s.pos = node_start[t];
+  s.end = node_start[t + 1];
+  CG_UNROLL for (int q = 0; q < 8; ++q) s.cur[q] = 0;
+  if (pmt_levels(k) > levels) return;  // (the host sizes `levels` from the deepest tx)
+  const uint32_t* pre = inc_prefix + c0;
+  pmt_walk(k, [&](uint32_t i) CG_LINLINE { return pre[i]; }, s);
+  CG_UNROLL for (int q = 0; q < 8; ++q) roots[(size_t)t * 8 + q] = bswap32_(s.cur[q]);
+}
+
 inline dim3 grid_for(uint32_t n) { return dim3((n + 255) / 256); }
 
 }  // namespace
@@ -370,6 +460,26 @@ hipError_t launch_pmt_eval(const uint32_t* node_start, const uint8_t* node_kind,
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(cg_pmt_eval, grid_for(n), dim3(256), 0, s, node_start, node_kind, node_hash, comp_start, leaves,
                      roots, n, stack, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_pmt_nonce(const uint32_t* fcomp_index, uint32_t n_fcomp, uint32_t n_comp,
+                            const uint32_t* comp_start, const uint32_t* comp_tx, const uint32_t* salts,
+                            uint32_t* nonces, hipStream_t s) {
+  if (n_fcomp == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pmt_nonce, grid_for(n_fcomp), dim3(256), 0, s, fcomp_index, n_fcomp, n_comp, comp_start,
+                     comp_tx, salts, nonces);
+  return hipGetLastError();
+}
+
+hipError_t launch_pmt_build(const uint32_t* leaves, const uint32_t* comp_start, const uint32_t* inc_prefix,
+                            const uint32_t* node_start, uint32_t n, uint32_t levels, uint32_t stride,
+                            uint32_t* park, uint8_t* node_kind, uint32_t* node_hash, uint32_t* roots,
+                            hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (stride < n) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cg_pmt_build, grid_for(n), dim3(256), 0, s, leaves, comp_start, inc_prefix, node_start, n,
+                     levels, stride, park, node_kind, node_hash, roots);
   return hipGetLastError();
 }
 

@@ -36,6 +36,11 @@ class WireTx:
     components: list[bytes]   # availableComponents order; last = serialized privacy salt
     salt: bytes               # PrivacySalt.bytes (32)
 
+    def build_filtered_transaction(self, ctx: _lib.Context, include: Sequence[object]) -> "FilteredTransaction":
+        """``wtx.buildFilteredTransaction(filtering)`` (WireTransaction.kt:97-98) on the device:
+        ``include[i]`` is the predicate's answer for component i (see build_filtered_batch)."""
+        return build_filtered_batch(ctx, [self], [include])[0]
+
 
 @dataclass
 class SignedTx:
@@ -386,3 +391,63 @@ def verify_filtered(ctx: _lib.Context, ftxs: Sequence[FilteredTransaction]) -> l
         if r == _lib.FTX_MALFORMED:
             raise IllegalArgumentException(f"filtered transaction {t}: partial tree is not a single tree")
     return [bool(r == _lib.FTX_TRUE) for r in res]
+
+
+# ------------------------------------------------------ building filtered transactions
+def build_filtered_batch(ctx: _lib.Context, wire_txs: Sequence[WireTx],
+                         include_masks: Sequence[Sequence[object]]) -> list[FilteredTransaction]:
+    """A loop of ``wtx.buildFilteredTransaction(filtering)`` (WireTransaction.kt:97-98 ->
+    FilteredTransaction.buildMerkleTransaction, MerkleTransaction.kt:159-166 ->
+    PartialMerkleTree.build, PartialMerkleTree.kt:66-123) in one device call
+    (cg_ftx_build_batch) — what NotaryFlow.Client does before it sends a transaction to a
+    non-validating notary (NotaryFlow.kt:72).  ``include_masks[t][i]`` is truthy when the
+    filtering predicate accepted component i of transaction t (one entry per component, the
+    serialized privacy salt included: its entry must be falsy).
+
+    Raises IllegalArgumentException for a mask that includes the salt (it can never be in
+    FilteredLeaves, MerkleTransaction.kt:112-117) or has the wrong length, and
+    MerkleTreeException for a transaction without components.  An empty mask gives the
+    object the JVM builds too: no filtered leaves and the tree ``Leaf(rootHash)``, whose
+    ``verify`` raises MerkleTreeException."""
+    if not wire_txs:
+        return []
+    if len(include_masks) != len(wire_txs):
+        raise IllegalArgumentException("one include mask per transaction")
+    for t, (w, m) in enumerate(zip(wire_txs, include_masks)):
+        if len(m) != len(w.components):
+            raise IllegalArgumentException(f"transaction {t}: one include entry per component")
+    arena, off, ln, start, salts = _pack_txs(wire_txs)
+    include = np.array([1 if x else 0 for m in include_masks for x in m] or [0], dtype=np.uint8)
+    n = len(wire_txs)
+    fstart = np.zeros(n + 1, dtype=np.uint32)
+    nstart = np.zeros(n + 1, dtype=np.uint32)
+    if ctx.lib.cg_ftx_build_layout(n, _lib.ptr(start), _lib.ptr(include), _lib.ptr(fstart), _lib.ptr(nstart)) != 0:
+        for t, (w, m) in enumerate(zip(wire_txs, include_masks)):
+            if w.components and m[-1]:
+                raise IllegalArgumentException(f"transaction {t}: the privacy salt cannot be a filtered component")
+        raise IllegalArgumentException("invalid transaction batch")
+    n_f, n_n = int(fstart[n]), int(nstart[n])
+    findex = np.zeros(max(n_f, 1), dtype=np.uint32)
+    nonces = np.zeros(32 * max(n_f, 1), dtype=np.uint8)
+    kind = np.zeros(max(n_n, 1), dtype=np.uint8)
+    nhash = np.zeros(32 * max(n_n, 1), dtype=np.uint8)
+    roots = np.zeros(32 * n, dtype=np.uint8)
+    st = ctx.lib.cg_ftx_build_batch(ctx.h, n, _lib.ptr(arena), len(arena), _lib.ptr(off), _lib.ptr(ln), _lib.ptr(start),
+                                    _lib.ptr(salts), _lib.ptr(include), n_f, n_n, _lib.ptr(fstart), _lib.ptr(findex),
+                                    _lib.ptr(nonces), _lib.ptr(nstart), _lib.ptr(kind), _lib.ptr(nhash),
+                                    _lib.ptr(roots))
+    if st == _lib.CG_E_MERKLE_EMPTY:
+        raise MerkleTreeException("Cannot calculate Merkle root on empty hash list.")
+    if st == _lib.CG_E_INVALID_ARGUMENT:
+        raise IllegalArgumentException((ctx.lib.cg_last_error(ctx.h) or b"").decode())
+    ctx.check(st)
+    out = []
+    for t, w in enumerate(wire_txs):
+        c0 = int(start[t])
+        js = range(int(fstart[t]), int(fstart[t + 1]))
+        leaves = FilteredLeaves([w.components[int(findex[j]) - c0] for j in js],
+                                [bytes(nonces[32 * j:32 * j + 32]) for j in js])
+        prog = [(int(kind[j]), bytes(nhash[32 * j:32 * j + 32])) for j in range(int(nstart[t]), int(nstart[t + 1]))]
+        out.append(FilteredTransaction(bytes(roots[32 * t:32 * t + 32]), leaves, PartialMerkleTree.from_postorder(prog)))
+    return out
+

@@ -73,8 +73,9 @@
 extern "C" {
 #endif
 
-/* The signing entry points (cg_signer_*, cg_sign_batch) are purely additive: no existing
- * signature or layout changed, so the version stays 4. */
+/* The signing entry points (cg_signer_*, cg_sign_batch) and the FilteredTransaction builder
+ * (cg_ftx_build_layout, cg_ftx_build_batch) are purely additive: no existing signature or
+ * layout changed, so the version stays 4. */
 #define CG_ABI_VERSION 4  /* 4: cg_set_option; the CORDA_AMD_* knobs read once, at cg_open */
 
 typedef int32_t cg_status;
@@ -257,6 +258,55 @@ cg_status cg_ftx_verify_batch(cg_ctx* ctx, size_t n_ftx, const uint8_t* arena, s
                               const uint64_t* comp_off, const uint32_t* comp_len, const uint32_t* comp_start,
                               const uint8_t* nonces, const uint32_t* node_start, const uint8_t* node_kind,
                               const uint8_t* node_hash, const uint8_t* root_hashes, uint8_t* result_out);
+
+/*
+ * FilteredTransaction construction (the producer of cg_ftx_verify_batch's input): a loop of
+ * wtx.buildFilteredTransaction(filtering) — what every client of a non-validating notary
+ * does once per notarisation (NotaryFlow.kt:72; oracle clients: RatesFixFlow.kt:65):
+ * WireTransaction.kt:97-98 -> FilteredTransaction.buildMerkleTransaction
+ * (MerkleTransaction.kt:159-166) -> PartialMerkleTree.build (PartialMerkleTree.kt:66-123) over
+ * the full tree of cg_txid_batch (leaf nonces SHA256(salt || BE32(i)), salt leaf
+ * SHA256(ser_salt), zero-hash padding to a power of two).
+ * Inputs: the transactions in cg_txid_batch's layout, and include[c] for every component c
+ * of the batch: non-zero = the filtering predicate accepted it.  Inclusion is by component
+ * INDEX; the JVM includes by leaf hash value, and the two agree because distinct indices of
+ * a transaction have distinct nonces.  Pad leaves are never included, so
+ * require(zeroHash !in includeHashes) cannot fire.  The last component of a transaction (the
+ * serialized privacy salt) can never be in FilteredLeaves (MerkleTransaction.kt:112-117): a
+ * non-zero include byte on it fails the whole call with CG_E_INVALID_ARGUMENT before anything
+ * is launched (the message names the transaction).
+ * Outputs, per tx t:
+ *   fcomp_start_out[t] .. fcomp_start_out[t+1]-1 (n_tx + 1 entries): its filtered components;
+ *     fcomp_index_out[j] = the batch-global index c of filtered component j (gather comp_off /
+ *     comp_len with it and hand the same arena to cg_ftx_verify_batch), nonces_out[32 j] its nonce
+ *   node_start_out[t] .. node_start_out[t+1]-1 (n_tx + 1 entries): its partial tree as the
+ *     post-order program of cg_ftx_verify_batch (node_kind_out 0 IncludedLeaf / 1 Leaf / 2
+ *     Node, node_hash_out[32 j]; a Node's 32 bytes are zero).  An inner node with an included
+ *     leaf below is a Node, any other subtree is cut to one Leaf(hash).  An empty mask gives
+ *     the single node Leaf(rootHash) and no filtered component: the JVM builds that object
+ *     too, and its verify() throws MerkleTreeException (CG_FTX_NO_LEAVES here).
+ *   root_out[32 t]: FilteredTransaction.rootHash = the id cg_txid_batch computes.
+ * A tx without components gets 0 nodes, 0 filtered components and a zero root, and the call
+ * returns CG_E_MERKLE_EMPTY with every other tx written, as cg_txid_batch does.
+ * The output sizes depend on the component counts and the mask only, never on a hash:
+ * cg_ftx_build_layout is a pure host function (no context, no device) that returns the two
+ * start arrays, whose last entries are the capacities to allocate.  cg_ftx_build_batch
+ * computes the layout again itself; with fcomp_cap (filtered components) or node_cap (nodes)
+ * too small it returns CG_E_INVALID_ARGUMENT, cg_last_error carries the needed counts and
+ * nothing is written.  More than 2^32 - 1 nodes: CG_E_INVALID_ARGUMENT.  Null pointers, a
+ * decreasing comp_start and a component outside the arena are CG_E_INVALID_ARGUMENT before
+ * the first copy or launch.
+ * Profiling spans: "merkle_leaf" (the leaf hashes), "pmt_nonce", "pmt_build".
+ */
+cg_status cg_ftx_build_layout(size_t n_tx, const uint32_t* comp_start, const uint8_t* include,
+                              uint32_t* fcomp_start_out, uint32_t* node_start_out);
+cg_status cg_ftx_build_batch(cg_ctx* ctx, size_t n_tx, const uint8_t* arena, size_t arena_bytes,
+                             const uint64_t* comp_off, const uint32_t* comp_len, const uint32_t* comp_start,
+                             const uint8_t* salts, const uint8_t* include, size_t fcomp_cap, size_t node_cap,
+                             uint32_t* fcomp_start_out, uint32_t* fcomp_index_out, uint8_t* nonces_out,
+                             uint32_t* node_start_out, uint8_t* node_kind_out, uint8_t* node_hash_out,
+                             uint8_t* root_out);
+
 /*
  * CompositeKey fulfilment over verification verdicts.  n_q queries; query q is a key
  * (plain or composite) as a post-order op program ops[prog_start[q] .. prog_start[q+1])
@@ -333,7 +383,7 @@ cg_status cg_release_cached(cg_ctx* ctx);
  * profiling is enabled.  Names: "ed25519_hash", "ed25519_points", "ed25519_msm",
  * "ecdsa_k1_prep", "ecdsa_k1_msm", "ecdsa_r1_prep", "ecdsa_r1_msm", "der_parse",
  * "merkle_leaf", "merkle_tree", "pmt_eval", "composite_eval", "stage", "ed25519_keyexp",
- * "ed25519_sign".
+ * "ed25519_sign", "pmt_nonce", "pmt_build".
  * enable: 0 off, 1 every span, 2 only the "call" span of each cg_verify_batch (its
  * GPU time from entry to the verdict download; two events per call).
  */

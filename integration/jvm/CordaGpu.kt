@@ -8,6 +8,8 @@ package net.corda.core.crypto.gpu
 import net.corda.core.contracts.PrivacySalt
 import net.corda.core.crypto.Crypto
 import net.corda.core.crypto.DigitalSignature
+import net.corda.core.crypto.MerkleTreeException
+import net.corda.core.crypto.PartialMerkleTree
 import net.corda.core.crypto.SignatureScheme
 import net.corda.core.crypto.TransactionSignature
 import net.corda.core.crypto.composite.CompositeKey
@@ -109,6 +111,56 @@ class CordaGpu(device: Int = 0) : AutoCloseable {
     }
 
     /**
+     * A loop of `wtx.buildFilteredTransaction(filtering)` (WireTransaction.kt:97-98 ->
+     * FilteredTransaction.buildMerkleTransaction, MerkleTransaction.kt:159-166 -> PartialMerkleTree.build,
+     * PartialMerkleTree.kt:66-123) in one device call: cg_ftx_build_layout sizes the outputs on the host,
+     * cg_ftx_build_batch fills them.  include: one byte per component of the arena, non-zero where the
+     * filtering predicate accepted it (never on a transaction's last component, the privacy salt:
+     * IllegalArgumentException).  A transaction without components: MerkleTreeException, as
+     * MerkleTree.getMerkleTree throws.
+     */
+    fun buildFilteredBatch(a: TxArena, include: ByteBuffer): FilteredBatch {
+        val fStart = direct(4 * (a.nTx + 1)); val nStart = direct(4 * (a.nTx + 1))
+        require(nativeFtxBuildLayout(a.nTx, a.compStart, include, fStart, nStart) == 0) {
+            "the include mask selects a privacy salt, or the component ranges are not monotone"
+        }
+        val nF = fStart.getInt(4 * a.nTx); val nN = nStart.getInt(4 * a.nTx)
+        val out = FilteredBatch(a.nTx, fStart, direct(4 * nF), direct(32 * nF), nStart, direct(nN), direct(32 * nN),
+                direct(32 * a.nTx))
+        val rc = buildFilteredBatch(handle, a.nTx, a.arena, a.compOff, a.compLen, a.compStart, a.salts, include,
+                out.fcompStart, out.fcompIndex, out.nonces, out.nodeStart, out.nodeKind, out.nodeHash, out.roots)
+        if (rc == CG_E_MERKLE_EMPTY) throw MerkleTreeException("Cannot calculate Merkle root on empty hash list.")
+        check(rc)
+        return out
+    }
+
+    /**
+     * cg_ftx_build_batch's outputs: per tx its filtered components (batch-global component indices and
+     * their nonces), its partial tree as the post-order program cg_ftx_verify_batch takes, and its root.
+     */
+    class FilteredBatch(val nTx: Int, val fcompStart: ByteBuffer, val fcompIndex: ByteBuffer, val nonces: ByteBuffer,
+                        val nodeStart: ByteBuffer, val nodeKind: ByteBuffer, val nodeHash: ByteBuffer,
+                        val roots: ByteBuffer) {
+        private fun hash(b: ByteBuffer, j: Int) = SecureHash.SHA256(ByteArray(32).also { b.position(32 * j); b.get(it) })
+
+        fun rootHash(t: Int): SecureHash = hash(roots, t)
+        /** Indices, within tx t's availableComponents, of its filtered components (compStart: the arena's). */
+        fun visible(t: Int, compStart: ByteBuffer): List<Int> =
+                (fcompStart.getInt(4 * t) until fcompStart.getInt(4 * t + 4)).map { fcompIndex.getInt(4 * it) - compStart.getInt(4 * t) }
+        fun nonces(t: Int): List<SecureHash> = (fcompStart.getInt(4 * t) until fcompStart.getInt(4 * t + 4)).map { hash(nonces, it) }
+        /** The PartialMerkleTree of tx t, rebuilt from its post-order program. */
+        fun partialMerkleTree(t: Int): PartialMerkleTree {
+            val st = ArrayList<PartialMerkleTree.PartialTree>()
+            for (j in nodeStart.getInt(4 * t) until nodeStart.getInt(4 * t + 4)) when (nodeKind.get(j).toInt()) {
+                0 -> st.add(PartialMerkleTree.PartialTree.IncludedLeaf(hash(nodeHash, j)))
+                1 -> st.add(PartialMerkleTree.PartialTree.Leaf(hash(nodeHash, j)))
+                else -> { val r = st.removeAt(st.size - 1); val l = st.removeAt(st.size - 1); st.add(PartialMerkleTree.PartialTree.Node(l, r)) }
+            }
+            return PartialMerkleTree(st.single())
+        }
+    }
+
+    /**
      * Ed25519 private keys expanded once on the device (cg_signer_create).  A key goes over as its
      * 32-byte seed, the form Ed25519PrivateKeySerializer writes (Kryo.kt:316-320); the direct buffer
      * that carried the seeds is zeroed before the constructor returns.
@@ -205,6 +257,13 @@ class CordaGpu(device: Int = 0) : AutoCloseable {
                                                 compLen: ByteBuffer, compStart: ByteBuffer, nonces: ByteBuffer,
                                                 nodeStart: ByteBuffer, nodeKind: ByteBuffer, nodeHash: ByteBuffer,
                                                 roots: ByteBuffer, result: ByteBuffer): Int
+        @JvmStatic external fun nativeFtxBuildLayout(nTx: Int, compStart: ByteBuffer, include: ByteBuffer,
+                                                     fcompStart: ByteBuffer, nodeStart: ByteBuffer): Int
+        @JvmStatic external fun buildFilteredBatch(handle: Long, nTx: Int, arena: ByteBuffer, compOff: ByteBuffer,
+                                                   compLen: ByteBuffer, compStart: ByteBuffer, salts: ByteBuffer,
+                                                   include: ByteBuffer, fcompStart: ByteBuffer, fcompIndex: ByteBuffer,
+                                                   nonces: ByteBuffer, nodeStart: ByteBuffer, nodeKind: ByteBuffer,
+                                                   nodeHash: ByteBuffer, roots: ByteBuffer): Int
         @JvmStatic external fun nativeSignerCreate(handle: Long, nKeys: Int, seeds: ByteBuffer): Long
         @JvmStatic external fun nativeSignerPublicKeys(handle: Long, signer: Long, pkOut: ByteBuffer): Int
         @JvmStatic external fun nativeSignerDestroy(handle: Long, signer: Long)
@@ -467,4 +526,31 @@ class NotaryBatchSigner(gpu: CordaGpu, notaryPrivateKey: EdDSAPrivateKey, privat
             signer.sign(txIds.map { it.bytes }).map { DigitalSignature.WithKey(notaryIdentityKey, it) }
 
     override fun close() = signer.close()
+}
+
+// ---------------------------------------------------------------- tear-offs (wtx.buildFilteredTransaction)
+/**
+ * Batch form of `wtxs.map { it.buildFilteredTransaction(filtering) }` — what NotaryFlow.Client does once
+ * per notarisation before it sends to a non-validating notary (NotaryFlow.kt:72:
+ * `stx.tx.buildFilteredTransaction { it is StateRef || it is TimeWindow }`) and an oracle client in
+ * RatesFixFlow.kt:65.  The predicate runs on the JVM, once per component, and only produces the include
+ * mask; the privacy salt (last of availableComponents) is never offered to it, as filterWithFun never
+ * offers it (WireTransaction.kt:108-117).  Returns, per tx, what buildMerkleTransaction assembles:
+ * the root hash, the indices of the visible components with their nonces, and the PartialMerkleTree.
+ * FilteredTransaction's constructor is private (MerkleTransaction.kt:147), so the last step —
+ * `FilteredTransaction(rootHash, wtx.filterWithFun(filtering) with these nonces, pmt)` — belongs in a
+ * companion function next to buildMerkleTransaction (INTEGRATION.md).
+ */
+class TearOff(val rootHash: SecureHash, val visible: List<Int>, val nonces: List<SecureHash>, val partialMerkleTree: PartialMerkleTree)
+
+fun buildFilteredTransactionsBatch(gpu: CordaGpu, wtxs: List<WireTransaction>, filtering: (Any) -> Boolean): List<TearOff> {
+    val arena = TxArena.of(wtxs, wtxs.map { 0 })
+    val include = direct(arena.compStart.getInt(4 * wtxs.size))
+    var c = 0
+    for (w in wtxs) {
+        val comps = w.availableComponents
+        for ((i, x) in comps.withIndex()) include.put(c++, if (i < comps.size - 1 && filtering(x)) 1 else 0)
+    }
+    val out = gpu.buildFilteredBatch(arena, include)
+    return wtxs.indices.map { t -> TearOff(out.rootHash(t), out.visible(t, arena.compStart), out.nonces(t), out.partialMerkleTree(t)) }
 }

@@ -11,6 +11,8 @@
  *   nativeSignerCreate/...  cg_signer_*              Ed25519 private keys expanded once on the device
  *   signBatch               cg_sign_batch            a loop of Crypto.doSign (Crypto.kt:394-401): the notary's
  *                                                    service.sign(txId.bytes) (NotaryFlow.kt:125-126)
+ *   nativeFtxBuildLayout    cg_ftx_build_layout      output sizes of the next one (host only)
+ *   buildFilteredBatch      cg_ftx_build_batch       a loop of wtx.buildFilteredTransaction (NotaryFlow.kt:72)
  *
  * Build on a JVM host against the JDK's jni.h:
  *   gcc -O2 -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include \
@@ -164,4 +166,46 @@ JNIEXPORT jint JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_signBatch(JNIEnv*
     return CG_E_INVALID_ARGUMENT;
   return cg_sign_batch(h > 0 ? CTX(h) : 0, (const cg_signer*)(intptr_t)signer, m, BUF(key_index), BUF(msg), CAP(msg),
                        BUF(msg_off), BUF(msg_len), BUF(sig_out), BUF(status));
+}
+
+/* FilteredTransaction construction (cg_ftx_build_layout, cg_ftx_build_batch:
+ * wtx.buildFilteredTransaction, MerkleTransaction.kt:159-166 -> PartialMerkleTree.kt:66-123).
+ * The layout call needs no context: it sizes the output buffers from the component counts
+ * and the include mask (one byte per component).  Every buffer's capacity is checked against
+ * n_tx before a start array is read. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_nativeFtxBuildLayout(JNIEnv* env, jclass cls,
+                                                                                    jint n_tx, jobject comp_start,
+                                                                                    jobject include,
+                                                                                    jobject fcomp_start,
+                                                                                    jobject node_start) {
+  if (n_tx < 0) return CG_E_INVALID_ARGUMENT;
+  const size_t m = (size_t)n_tx;
+  if (CAP(comp_start) < 4 * (m + 1) || CAP(fcomp_start) < 4 * (m + 1) || CAP(node_start) < 4 * (m + 1))
+    return CG_E_INVALID_ARGUMENT;
+  const uint32_t* cs = (const uint32_t*)BUF(comp_start);
+  if (CAP(include) < cs[m]) return CG_E_INVALID_ARGUMENT;
+  return cg_ftx_build_layout(m, cs, BUF(include), BUF(fcomp_start), BUF(node_start));
+}
+
+/* One call per batch.  The capacities handed to the library are what the output buffers
+ * hold: filtered components = min(fcomp_index / 4, nonces / 32), nodes = min(node_kind,
+ * node_hash / 32); too small comes back as CG_E_INVALID_ARGUMENT with the needed counts in
+ * nativeLastError. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_buildFilteredBatch(
+    JNIEnv* env, jclass cls, jlong h, jint n_tx, jobject arena, jobject comp_off, jobject comp_len, jobject comp_start,
+    jobject salts, jobject include, jobject fcomp_start, jobject fcomp_index, jobject nonces, jobject node_start,
+    jobject node_kind, jobject node_hash, jobject roots) {
+  if (n_tx < 0) return CG_E_INVALID_ARGUMENT;
+  const size_t m = (size_t)n_tx;
+  if (CAP(comp_start) < 4 * (m + 1) || CAP(fcomp_start) < 4 * (m + 1) || CAP(node_start) < 4 * (m + 1) ||
+      CAP(salts) < 32 * m || CAP(roots) < 32 * m)
+    return CG_E_INVALID_ARGUMENT;
+  const size_t n_comp = ((const uint32_t*)BUF(comp_start))[m];
+  if (CAP(include) < n_comp || CAP(comp_off) < 8 * n_comp || CAP(comp_len) < 4 * n_comp) return CG_E_INVALID_ARGUMENT;
+  size_t fcap = CAP(fcomp_index) / 4, ncap = CAP(node_kind);
+  if (CAP(nonces) / 32 < fcap) fcap = CAP(nonces) / 32;
+  if (CAP(node_hash) / 32 < ncap) ncap = CAP(node_hash) / 32;
+  return cg_ftx_build_batch(h > 0 ? CTX(h) : 0, m, BUF(arena), CAP(arena), BUF(comp_off), BUF(comp_len),
+                            BUF(comp_start), BUF(salts), BUF(include), fcap, ncap, BUF(fcomp_start), BUF(fcomp_index),
+                            BUF(nonces), BUF(node_start), BUF(node_kind), BUF(node_hash), BUF(roots));
 }
