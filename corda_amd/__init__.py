@@ -8,8 +8,8 @@ transactions (transactions.py), CompositeKey fulfilment (composite.py) and the
 multi-GPU sharding driver (dist.py).
 """
 from ._lib import Context, CordaGpuError, load  # noqa: F401
-from .crypto import (Ed25519Signer, SigningException, do_sign_batch, entropy_to_seed,  # noqa: F401
-                     sign_batch)
+from .crypto import (EcdsaSigner, Ed25519Signer, SigningException, do_sign_batch,  # noqa: F401
+                     ecdsa_sign_batch, ecdsa_sign_packed, entropy_to_seed, sign_batch)
 
 __all__ = ["Context", "CordaGpuError", "load", "Ed25519Signer", "SigningException", "do_sign_batch",
-           "entropy_to_seed", "sign_batch"]
+           "entropy_to_seed", "sign_batch", "EcdsaSigner", "ecdsa_sign_batch", "ecdsa_sign_packed"]

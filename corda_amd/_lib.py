@@ -36,6 +36,11 @@ ABI_VERSION = 4
 # per-element outcomes of cg_sign_batch, and the elements it processes at a time (CG_SIGN_CHUNK)
 SIGN_OK, SIGN_EMPTY = 0, 1
 SIGN_CHUNK = 1 << 20
+# cg_ecdsa_sign_batch: further outcomes (precedence EMPTY > NONCE_INVALID > DEGENERATE), the nonce
+# modes, and the longest DER signature (CG_ECDSA_SIG_MAX, the least sig_stride)
+SIGN_NONCE_INVALID, SIGN_DEGENERATE = 2, 3
+ECDSA_NONCE_RFC6979, ECDSA_NONCE_CALLER = 0, 1
+ECDSA_SIG_MAX = 72
 
 # exported symbols and their prototypes: (restype, argtypes)
 _u8p, _u32p, _u64p, _i32p = POINTER(c_uint8), POINTER(c_uint32), POINTER(c_uint64), POINTER(ctypes.c_int32)
@@ -84,6 +89,13 @@ PROTOTYPES = {
     "cg_signer_destroy": (None, [c_void_p, c_void_p]),
     "cg_sign_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                               c_void_p, c_void_p]),
+    "cg_ecdsa_signer_create": (c_int, [c_void_p, c_int, c_size_t, c_void_p, POINTER(c_void_p)]),
+    "cg_ecdsa_signer_size": (c_size_t, [c_void_p]),
+    "cg_ecdsa_signer_scheme": (c_int, [c_void_p]),
+    "cg_ecdsa_signer_public_keys": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "cg_ecdsa_signer_destroy": (None, [c_void_p, c_void_p]),
+    "cg_ecdsa_sign_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                    c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -260,8 +260,10 @@ class PreparedBatch:
 # ``Crypto.doSign(privateKey, clearData)`` (Crypto.kt:394-401) for EDDSA_ED25519_SHA512
 # keys, batched: what a notary does to every transaction id it accepts
 # (NotaryFlow.kt:125-126 -> NotaryService.kt:75-77 -> keyManagementService.sign).  i2p's
-# EdDSAEngine signs deterministically (RFC 8032), so the 64 bytes equal the JVM's.  ECDSA
-# signing stays on the JVM: BC 1.57 draws its nonce from SecureRandom.
+# EdDSAEngine signs deterministically (RFC 8032), so the 64 bytes equal the JVM's.  EC keys
+# sign through EcdsaSigner / ecdsa_sign_batch: BC's ECDSASigner.generateSignature is a pure
+# function of (d, e, k), so with the nonce k given by the caller (drawn as BC draws it) the DER
+# bytes equal BC's, and with RFC 6979 nonces derived on the device no randomness is needed.
 SIGN_OK, SIGN_EMPTY = _lib.SIGN_OK, _lib.SIGN_EMPTY
 
 
@@ -360,21 +362,144 @@ def sign_batch(ctx: _lib.Context, signer: Ed25519Signer, clear_data: Sequence[by
     return sign_packed(ctx, signer, arena, msg_off, msg_len, key_index)
 
 
-def do_sign_batch(ctx: _lib.Context, signer: Ed25519Signer, clear_data: Sequence[bytes], key_index=None,
-                  verify_after_sign: bool = False) -> list[bytes]:
-    """``for i in range(n): Crypto.doSign(key[key_index[i]], clear_data[i])``: the n
-    signatures, or the exception of the lowest failing index.  verify_after_sign: every
-    signature is verified on the device before any is returned, the usual guard against a
-    faulted computation leaking the key."""
-    sig, status = sign_batch(ctx, signer, clear_data, key_index)
+class EcdsaSigner:
+    """EC private keys of one curve held on the device (``cg_ecdsa_signer_create``).
+    ``scheme``: ECDSA_SECP256K1_SHA256 or ECDSA_SECP256R1_SHA256 (or its id 2 / 3);
+    ``private_scalars``: d per key as an int or as 32 big-endian bytes, 0 < d < n."""
+
+    def __init__(self, ctx: _lib.Context, scheme, private_scalars: Sequence):
+        self.scheme = _scheme_id(scheme)
+        rows = [int(d).to_bytes(32, "big") if isinstance(d, int) else bytes(d) for d in private_scalars]
+        if any(len(r) != 32 for r in rows):
+            raise IllegalArgumentException("an EC private scalar is 32 big-endian bytes")
+        self.ctx, self.n_keys, self.h = ctx, len(rows), None
+        buf = np.frombuffer(b"".join(rows) or bytes(32), dtype=np.uint8).copy()
+        h = _lib.c_void_p()
+        try:
+            ctx.check(ctx.lib.cg_ecdsa_signer_create(ctx.h, self.scheme, self.n_keys, _lib.ptr(buf),
+                                                     _lib.ctypes.byref(h)))
+        finally:
+            buf[:] = 0  # this module's own copy of the scalars
+        self.h = h
+        self._pk = None
+
+    @property
+    def public_keys(self) -> list[bytes]:
+        """Q = d G per key as 64 bytes X || Y: the key form ``pack`` takes for the ECDSA schemes."""
+        if self._pk is None:
+            out = np.zeros((max(self.n_keys, 1), 64), dtype=np.uint8)
+            self.ctx.check(self.ctx.lib.cg_ecdsa_signer_public_keys(self.ctx.h, self.h, _lib.ptr(out)))
+            self._pk = [out[j].tobytes() for j in range(self.n_keys)]
+        return list(self._pk)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.ctx.h:  # (a closed context has already released the device arrays)
+                self.ctx.lib.cg_ecdsa_signer_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SIGN_NONCE_INVALID, SIGN_DEGENERATE = _lib.SIGN_NONCE_INVALID, _lib.SIGN_DEGENERATE
+
+
+def ecdsa_sign_packed(ctx: _lib.Context, signer: EcdsaSigner, msg: np.ndarray, msg_off: np.ndarray,
+                      msg_len: np.ndarray, key_index: np.ndarray | None = None, nonces: np.ndarray | None = None,
+                      sig_stride: int = _lib.ECDSA_SIG_MAX):
+    """``cg_ecdsa_sign_batch`` on arrays in the C ABI's layout; ``nonces``: [n, 32] uint8
+    big-endian rows (caller mode) or None (RFC 6979).  Returns (signatures [n, sig_stride]
+    uint8, sig_len [n] uint32, status [n] uint8): the sig / sig_len arrays of ``PackedBatch``."""
+    n = len(msg_len)
+    msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+    msg_len = np.ascontiguousarray(msg_len, dtype=np.uint32)
+    if key_index is not None:
+        key_index = np.ascontiguousarray(key_index, dtype=np.uint32)
+        if len(key_index) != n:
+            raise IllegalArgumentException("key_index and clear_data differ in length")
+    if len(msg_off) != n:
+        raise IllegalArgumentException("msg_off and msg_len differ in length")
+    mode = _lib.ECDSA_NONCE_RFC6979
+    if nonces is not None:
+        mode = _lib.ECDSA_NONCE_CALLER
+        nonces = np.ascontiguousarray(nonces, dtype=np.uint8).reshape(-1, 32)
+        if len(nonces) != n:
+            raise IllegalArgumentException("nonces and clear_data differ in length")
+        if n == 0:
+            nonces = np.zeros((1, 32), dtype=np.uint8)
+    sig = np.zeros((max(n, 1), sig_stride), dtype=np.uint8)
+    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
+    status = np.zeros(max(n, 1), dtype=np.uint8)
+    ctx.check(ctx.lib.cg_ecdsa_sign_batch(ctx.h, signer.h, n, _lib.ptr(key_index), _lib.ptr(msg), len(msg),
+                                          _lib.ptr(msg_off), _lib.ptr(msg_len), mode, _lib.ptr(nonces), _lib.ptr(sig),
+                                          sig_stride, _lib.ptr(sig_len), _lib.ptr(status)))
+    return sig[:n], sig_len[:n], status[:n]
+
+
+def ecdsa_sign_batch(ctx: _lib.Context, signer: EcdsaSigner, clear_data: Sequence[bytes], key_index=None, nonces=None):
+    """Signs clear_data[i] with key key_index[i] of the signer (None: key 0 throughout).
+    ``nonces``: None for RFC 6979 nonces derived on the device, or one k per element (int or
+    32 big-endian bytes) drawn as BC's RandomDSAKCalculator draws it.  Returns (DER signatures
+    as a list of bytes, status [n]): SIGN_OK, or b"" with SIGN_EMPTY / SIGN_NONCE_INVALID /
+    SIGN_DEGENERATE."""
+    n = len(clear_data)
+    msg_len = np.array([len(m) for m in clear_data], dtype=np.uint32)
+    msg_off = np.zeros(n, dtype=np.uint64)
+    if n:
+        msg_off[1:] = np.cumsum(msg_len[:-1], dtype=np.uint64)
+    arena = np.frombuffer(b"".join(bytes(m) for m in clear_data) or b"\0", dtype=np.uint8).copy()
+    rows = None
+    if nonces is not None:
+        if len(nonces) != n:
+            raise IllegalArgumentException("nonces and clear_data differ in length")
+        rows = np.frombuffer(b"".join(int(k).to_bytes(32, "big") if isinstance(k, int) else bytes(k) for k in nonces),
+                             dtype=np.uint8).copy().reshape(-1, 32) if n else np.zeros((0, 32), dtype=np.uint8)
+    sig, sig_len, status = ecdsa_sign_packed(ctx, signer, arena, msg_off, msg_len, key_index, rows)
+    if rows is not None:
+        rows[:] = 0
+    return [sig[i, :sig_len[i]].tobytes() for i in range(n)], status
+
+
+_SIGN_FAILURES = {
+    _lib.SIGN_EMPTY: "Signing of an empty array is not permitted!",
+    _lib.SIGN_NONCE_INVALID: "the nonce is outside [1, n-1]",
+    _lib.SIGN_DEGENERATE: "the nonce gives r = 0 or s = 0",
+}
+
+
+def do_sign_batch(ctx: _lib.Context, signer, clear_data: Sequence[bytes], key_index=None,
+                  verify_after_sign: bool = False, nonces=None) -> list[bytes]:
+    """``for i in range(n): Crypto.doSign(key[key_index[i]], clear_data[i])`` for an
+    ``Ed25519Signer`` or an ``EcdsaSigner``: the n signatures, or the exception of the lowest
+    failing index.  ``nonces`` (EcdsaSigner only): as in ``ecdsa_sign_batch``.
+    verify_after_sign: every signature is verified on the device before any is returned, the
+    usual guard against a faulted computation leaking the key."""
+    if isinstance(signer, EcdsaSigner):
+        sigs, status = ecdsa_sign_batch(ctx, signer, clear_data, key_index, nonces)
+        scheme = signer.scheme
+    else:
+        if nonces is not None:
+            raise IllegalArgumentException("nonces apply to an EcdsaSigner only")
+        sig, status = sign_batch(ctx, signer, clear_data, key_index)
+        sigs = [sig[i].tobytes() for i in range(len(clear_data))]
+        scheme = EDDSA_ED25519_SHA512
     bad = np.flatnonzero(status != SIGN_OK)
     if bad.size:
-        raise SigningException("Signing of an empty array is not permitted!", int(bad[0]))
-    sigs = [sig[i].tobytes() for i in range(len(clear_data))]
+        raise SigningException(_SIGN_FAILURES.get(int(status[bad[0]]), "signing failed"), int(bad[0]))
     if verify_after_sign and sigs:
         pks = signer.public_keys
         idx = np.zeros(len(sigs), dtype=np.int64) if key_index is None else np.asarray(key_index, dtype=np.int64)
-        v = is_valid_batch(ctx, EDDSA_ED25519_SHA512, [pks[int(j)] for j in idx], sigs, clear_data)
+        v = is_valid_batch(ctx, scheme, [pks[int(j)] for j in idx], sigs, clear_data)
         wrong = np.flatnonzero(v != ACCEPT)
         if wrong.size:
             raise SigningException("signature failed verification after signing", int(wrong[0]))

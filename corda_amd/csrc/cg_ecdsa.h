@@ -698,21 +698,27 @@ CG_HD void ecdsa_q_table_affine(const uint32_t qx[8], const uint32_t qy[8], Put&
   });
 }
 
+// The generator G, affine (Z = 1), Montgomery form.
+template <class C>
+CG_HD void ec_generator(jpt& g) {
+  const uint32_t k1x[8] = {0x16F81798u, 0x59F2815Bu, 0x2DCE28D9u, 0x029BFCDBu, 0xCE870B07u, 0x55A06295u, 0xF9DCBBACu, 0x79BE667Eu};
+  const uint32_t k1y[8] = {0xFB10D4B8u, 0x9C47D08Fu, 0xA6855419u, 0xFD17B448u, 0x0E1108A8u, 0x5DA4FBFCu, 0x26A3C465u, 0x483ADA77u};
+  const uint32_t r1x[8] = {0xD898C296u, 0xF4A13945u, 0x2DEB33A0u, 0x77037D81u, 0x63A440F2u, 0xF8BCE6E5u, 0xE12C4247u, 0x6B17D1F2u};
+  const uint32_t r1y[8] = {0x37BF51F5u, 0xCBB64068u, 0x6B315ECEu, 0x2BCE3357u, 0x7C0F9E16u, 0x8EE7EB4Au, 0xFE1A7F9Bu, 0x4FE342E2u};
+  f26_from_u256<C>(g.X, C::kScheme == 2 ? k1x : r1x);
+  f26_from_u256<C>(g.Y, C::kScheme == 2 ? k1y : r1y);
+  F26<C>::one(g.Z);
+  g.inf = 0;
+}
+
 // Affine k*G (or k*2^128 G, shift128 = 1; 1 <= k < 2^17) in Montgomery form for the
 // shared generator tables: left-to-right binary with the exact formulas, then one
 // inversion.  One lane per entry at context creation (and on the host for the tests).
 template <class C>
 CG_HD void ecdsa_g_entry(uint32_t k, f26& x, f26& y, uint32_t shift128 = 0) {
-  const uint32_t k1x[8] = {0x16F81798u, 0x59F2815Bu, 0x2DCE28D9u, 0x029BFCDBu, 0xCE870B07u, 0x55A06295u, 0xF9DCBBACu, 0x79BE667Eu};
-  const uint32_t k1y[8] = {0xFB10D4B8u, 0x9C47D08Fu, 0xA6855419u, 0xFD17B448u, 0x0E1108A8u, 0x5DA4FBFCu, 0x26A3C465u, 0x483ADA77u};
-  const uint32_t r1x[8] = {0xD898C296u, 0xF4A13945u, 0x2DEB33A0u, 0x77037D81u, 0x63A440F2u, 0xF8BCE6E5u, 0xE12C4247u, 0x6B17D1F2u};
-  const uint32_t r1y[8] = {0x37BF51F5u, 0xCBB64068u, 0x6B315ECEu, 0x2BCE3357u, 0x7C0F9E16u, 0x8EE7EB4Au, 0xFE1A7F9Bu, 0x4FE342E2u};
   jpt g, acc;
-  f26_from_u256<C>(g.X, C::kScheme == 2 ? k1x : r1x);
-  f26_from_u256<C>(g.Y, C::kScheme == 2 ? k1y : r1y);
-  F26<C>::one(g.Z);
+  ec_generator<C>(g);
   CG_UNROLL for (int i = 0; i < 10; ++i) acc.X.v[i] = acc.Y.v[i] = acc.Z.v[i] = 0;
-  g.inf = 0;
   acc.inf = 1;
   CG_NOUNROLL for (uint32_t i = 0; i < 128 * shift128; ++i) ec_dbl<C>(g, g);  // 2^128 G (its own table)
   if (shift128) {  // back to affine: the table loop adds g with the mixed formula

@@ -43,4 +43,36 @@ hipError_t launch_der_parse(int scheme, const uint8_t* sig, size_t stride, const
                             uint32_t fill_len, const uint32_t* idx, uint32_t n, uint32_t cap, uint32_t* rs,
                             uint32_t* der, hipStream_t s);
 
+// Signing (K11, cg_ecdsa_sign.h).  The per-window tables of one curve (ecdsa_sign_tab_words()
+// words, built once by launch_ecdsa_signtab_build); the signer's keys d [8][n_keys] LE limbs;
+// one chunk of <= cap elements through scratch sized for cap: status[cap], ework[8 cap],
+// xw[10 cap], invn / invp (ecdsa_sign_inv_words(cap, 8 / 10) words: they hold k, k^-1 and
+// products of them, so the caller zeroes them before reuse).  Stage 0: hash, nonce, R = k G;
+// stage 1: the two batched inversions; stage 2: r, s, DER -> sig (72-byte rows, zero past the
+// signature), sig_len[i] (0 unless signed), status_out[i] (CG_SIGN_*).
+struct EcdsaSignDev {
+  int scheme = 0;
+  const uint32_t* tab = nullptr;
+  const uint32_t* key_index = nullptr;  // [n], or null: key 0
+  const uint32_t* d = nullptr;
+  uint32_t n_keys = 0;
+  const uint8_t* arena = nullptr;
+  const uint64_t* msg_off = nullptr;
+  const uint32_t* msg_len = nullptr;
+  uint32_t nonce_mode = 0;
+  const uint32_t* k_rows = nullptr;  // [n] rows of 32 big-endian bytes (caller mode)
+  uint32_t cap = 0;
+  uint32_t *status = nullptr, *ework = nullptr, *xw = nullptr, *invn = nullptr, *invp = nullptr;
+  uint8_t* sig = nullptr;
+  uint32_t* sig_len = nullptr;
+  uint8_t* status_out = nullptr;
+};
+size_t ecdsa_sign_tab_words();
+size_t ecdsa_sign_inv_words(uint32_t cap, int words);
+hipError_t launch_ecdsa_signtab_build(int scheme, uint32_t* tab, hipStream_t s);
+// pub: 64-byte rows X || Y (big-endian), the verify key form
+hipError_t launch_ecdsa_sign_keyexp(int scheme, const uint32_t* tab, const uint32_t* d, uint32_t n_keys, uint32_t* pub,
+                                    hipStream_t s);
+hipError_t launch_ecdsa_sign_stage(const EcdsaSignDev& d, uint32_t n, int stage, hipStream_t s);
+
 }  // namespace cg

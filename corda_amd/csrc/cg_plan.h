@@ -110,6 +110,7 @@ enum Opt : int {
   OPT_FTX_MIN_CHUNK,
   OPT_FTX_TAIL,
   OPT_FTX_BUILD_CHUNK,
+  OPT_ECDSA_SIGN_CHUNK,
   OPT_TIMELINE,
   OPT_COUNT
 };
@@ -126,7 +127,7 @@ inline const char* opt_name(int o) {
       "CORDA_AMD_RING_MAX_MB",       "CORDA_AMD_COPY_THREADS",      "CORDA_AMD_TX_CHUNKS",
       "CORDA_AMD_TX_MIN_CHUNK",      "CORDA_AMD_TX_TAIL",           "CORDA_AMD_TX_CURVE_ON_HASH",
       "CORDA_AMD_FTX_CHUNKS",        "CORDA_AMD_FTX_MIN_CHUNK",     "CORDA_AMD_FTX_TAIL",
-      "CORDA_AMD_FTX_BUILD_CHUNK",   "CORDA_AMD_TIMELINE"};
+      "CORDA_AMD_FTX_BUILD_CHUNK",   "CORDA_AMD_ECDSA_SIGN_CHUNK",  "CORDA_AMD_TIMELINE"};
   return o >= 0 && o < OPT_COUNT ? k[o] : nullptr;
 }
 

@@ -40,6 +40,7 @@
 #include "cg_ftx_layout.h"
 #include "cg_kernels.h"
 #include "cg_merkle_api.h"
+#include "cg_mp256.h"
 #include "cg_plan.h"
 
 namespace {
@@ -271,6 +272,9 @@ struct cg_ctx {
   // final sync
   std::vector<hipEvent_t> sync_event_pool;
   cg::EcdsaConsts* ec = nullptr;
+  // the fixed-base tables of ECDSA signing, per curve (secp256k1, secp256r1): built by the
+  // curve's first cg_ecdsa_signer_create, live blocks of the context until cg_close
+  uint32_t* ecsign_tab[2] = {nullptr, nullptr};
   // device block cache: size -> free block; live block -> size
   std::multimap<size_t, void*> free_blocks;
   std::unordered_map<void*, size_t> live_blocks;
@@ -3721,6 +3725,282 @@ cg_status cg_sign_batch(cg_ctx* ctx, const cg_signer* s, size_t n, const uint32_
   (void)hipStreamSynchronize(ctx->stream);
   for (const void* p : {(const void*)arena_d, (const void*)off_d, (const void*)len_d, (const void*)idx_d,
                         (const void*)sig_d, (const void*)stat_d})
+    dfree(ctx, p);
+  collect_timings(ctx);
+  return st;
+  CG_API_END(ctx)
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- ECDSA signing (K11)
+// Device-resident signer of one curve: the private scalars d, SoA over the keys ([8][n_keys]
+// LE limbs; ecdsa_kernels.hip), and their public keys as 64-byte rows.  d is secret: both
+// arrays are zeroed before their blocks go back to the context's cache.
+struct cg_ecdsa_signer {
+  int scheme = 0;
+  size_t n_keys = 0;
+  uint32_t* d = nullptr;
+  uint32_t* pub = nullptr;  // [16 n_keys] X || Y, big-endian bytes
+};
+
+namespace {
+
+void ecdsa_signer_free(cg_ctx* ctx, cg_ecdsa_signer* s) {
+  if (!s) return;
+  wipe_free(ctx, s->d, 8 * s->n_keys * sizeof(uint32_t));
+  wipe_free(ctx, s->pub, 16 * s->n_keys * sizeof(uint32_t));
+  delete s;
+}
+
+// The order n of the curve as 32 big-endian bytes.
+void ecdsa_order_be(int scheme, uint8_t out[32]) {
+  uint32_t nn[8];
+  if (scheme == 2) cg::CurveK1::n(nn); else cg::CurveR1::n(nn);
+  for (int i = 0; i < 8; ++i)
+    for (int b = 0; b < 4; ++b) out[31 - 4 * i - b] = (uint8_t)(nn[i] >> (8 * b));
+}
+
+// The curve's fixed-base signing tables: built by the first signer of the curve, kept until
+// cg_close (a live block of the context).
+cg_status ecdsa_sign_tables(cg_ctx* ctx, int scheme) {
+  uint32_t*& tab = ctx->ecsign_tab[scheme == 2 ? 0 : 1];
+  if (tab) return CG_OK;
+  uint32_t* t = nullptr;
+  cg_status st = dalloc(ctx, &t, cg::ecdsa_sign_tab_words(), "alloc ecdsa signing tables");
+  if (st != CG_OK) return st;
+  hipError_t e;
+  {
+    Timed tm(ctx, "ecdsa_signtab", cg::ecdsa_sign_tab_words() / 32);
+    e = cg::launch_ecdsa_signtab_build(scheme, t, ctx->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    dfree(ctx, t);
+    return hip_fail(ctx, e, "ecdsa signing tables");
+  }
+  tab = t;
+  return CG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+cg_status cg_ecdsa_signer_create(cg_ctx* ctx, int scheme, size_t n_keys, const uint8_t* d_be, cg_ecdsa_signer** out) {
+  CG_API_BEGIN
+  if (!ctx) return CG_E_INVALID_ARGUMENT;
+  if (!out) return fail(ctx, CG_E_INVALID_ARGUMENT, "null signer output");
+  *out = nullptr;
+  if (scheme != CG_SCHEME_ECDSA_SECP256K1_SHA256 && scheme != CG_SCHEME_ECDSA_SECP256R1_SHA256)
+    return fail(ctx, CG_E_INVALID_ARGUMENT, "an ECDSA signer's scheme is 2 (secp256k1) or 3 (secp256r1)");
+  if (n_keys && !d_be) return fail(ctx, CG_E_INVALID_ARGUMENT, "null private scalars");
+  if (n_keys > 0xFFFFFFF0ull) return fail(ctx, CG_E_INVALID_ARGUMENT, "more than 2^32 - 16 keys");
+  {
+    uint8_t order[32];
+    ecdsa_order_be(scheme, order);
+    static const uint8_t zero[32] = {0};
+    for (size_t j = 0; j < n_keys; ++j)  // 0 < d < n (the message names the key, never its bytes)
+      if (std::memcmp(d_be + 32 * j, zero, 32) == 0 || std::memcmp(d_be + 32 * j, order, 32) >= 0)
+        return fail(ctx, CG_E_INVALID_ARGUMENT, "private scalar outside [1, n-1] at key " + std::to_string(j));
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, CG_E_DEVICE, "hipSetDevice");
+  cg_ecdsa_signer* s = new (std::nothrow) cg_ecdsa_signer();
+  if (!s) return fail(ctx, CG_E_OUT_OF_MEMORY, "host allocation failed");
+  s->scheme = scheme;
+  s->n_keys = n_keys;
+  if (n_keys == 0) {  // nothing to expand, nothing to launch
+    *out = s;
+    return CG_OK;
+  }
+  cg_status st;
+  if ((st = ecdsa_sign_tables(ctx, scheme)) == CG_OK &&
+      (st = dalloc(ctx, &s->d, 8 * n_keys, "alloc signer scalars")) == CG_OK &&
+      (st = dalloc(ctx, &s->pub, 16 * n_keys, "alloc signer public keys")) == CG_OK) {
+    // big-endian rows -> limb-major words: the one host staging copy, wiped once uploaded
+    std::vector<uint32_t> limbs(8 * n_keys);
+    for (size_t j = 0; j < n_keys; ++j)
+      for (int w = 0; w < 8; ++w) {
+        const uint8_t* p = d_be + 32 * j + 4 * (7 - w);
+        limbs[(size_t)w * n_keys + j] = (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
+      }
+    hipError_t e = hipMemcpyAsync(s->d, limbs.data(), limbs.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+      Timed t(ctx, "ecdsa_keyexp", n_keys);
+      e = cg::launch_ecdsa_sign_keyexp(scheme, ctx->ecsign_tab[scheme == 2 ? 0 : 1], s->d, (uint32_t)n_keys, s->pub,
+                                       ctx->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    volatile uint32_t* lv = limbs.data();
+    for (size_t k = 0; k < limbs.size(); ++k) lv[k] = 0;
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) st = hip_fail(ctx, e, "ecdsa key expansion");
+  }
+  collect_timings(ctx);
+  if (st != CG_OK) {
+    ecdsa_signer_free(ctx, s);
+    return st;
+  }
+  *out = s;
+  return CG_OK;
+  CG_API_END(ctx)
+}
+
+size_t cg_ecdsa_signer_size(const cg_ecdsa_signer* s) { return s ? s->n_keys : 0; }
+
+int cg_ecdsa_signer_scheme(const cg_ecdsa_signer* s) { return s ? s->scheme : 0; }
+
+cg_status cg_ecdsa_signer_public_keys(cg_ctx* ctx, const cg_ecdsa_signer* s, uint8_t* xy_out) {
+  CG_API_BEGIN
+  if (!ctx) return CG_E_INVALID_ARGUMENT;
+  if (!s) return fail(ctx, CG_E_INVALID_ARGUMENT, "null signer");
+  if (s->n_keys == 0) return CG_OK;
+  if (!xy_out) return fail(ctx, CG_E_INVALID_ARGUMENT, "null xy_out");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, CG_E_DEVICE, "hipSetDevice");
+  CG_TRY(ctx, hipMemcpyAsync(xy_out, s->pub, 64 * s->n_keys, hipMemcpyDeviceToHost, ctx->stream),
+         "download public keys");
+  CG_TRY(ctx, hipStreamSynchronize(ctx->stream), "download public keys");
+  return CG_OK;
+  CG_API_END(ctx)
+}
+
+void cg_ecdsa_signer_destroy(cg_ctx* ctx, cg_ecdsa_signer* s) {
+  try {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    ecdsa_signer_free(ctx, s);
+  } catch (...) {
+    api_guard_fail(ctx);
+  }
+}
+
+cg_status cg_ecdsa_sign_batch(cg_ctx* ctx, const cg_ecdsa_signer* s, size_t n, const uint32_t* key_index,
+                              const uint8_t* msg, size_t msg_bytes, const uint64_t* msg_off, const uint32_t* msg_len,
+                              int nonce_mode, const uint8_t* k_be, uint8_t* sig_out, size_t sig_stride,
+                              uint32_t* sig_len_out, uint8_t* status_out) {
+  CG_API_BEGIN
+  if (!ctx) return CG_E_INVALID_ARGUMENT;
+  if (!s) return fail(ctx, CG_E_INVALID_ARGUMENT, "null signer");
+  if (nonce_mode != CG_ECDSA_NONCE_RFC6979 && nonce_mode != CG_ECDSA_NONCE_CALLER)
+    return fail(ctx, CG_E_INVALID_ARGUMENT, "unknown nonce mode");
+  if (sig_stride < CG_ECDSA_SIG_MAX) return fail(ctx, CG_E_INVALID_ARGUMENT, "sig_stride below CG_ECDSA_SIG_MAX (72)");
+  if (n == 0) return CG_OK;
+  if (n > 0xFFFFFFF0ull) return fail(ctx, CG_E_INVALID_ARGUMENT, "batch larger than 2^32 - 16 elements");
+  if (!sig_out || !sig_len_out || !msg_off || !msg_len || (msg_bytes > 0 && !msg))
+    return fail(ctx, CG_E_INVALID_ARGUMENT, "null input pointer");
+  if (nonce_mode == CG_ECDSA_NONCE_CALLER && !k_be)
+    return fail(ctx, CG_E_INVALID_ARGUMENT, "null k_be in caller nonce mode");
+  if (s->n_keys == 0) return fail(ctx, CG_E_INVALID_ARGUMENT, "the signer holds no keys");
+  for (size_t i = 0; key_index && i < n; ++i)
+    if (key_index[i] >= s->n_keys)
+      return fail(ctx, CG_E_INVALID_ARGUMENT, "key_index out of range at element " + std::to_string(i));
+  {
+    const size_t i = first_out_of_arena(msg_off, msg_len, n, msg_bytes);
+    if (i < n) return fail(ctx, CG_E_INVALID_ARGUMENT, out_of_arena_message(i));
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, CG_E_DEVICE, "hipSetDevice");
+  // the whole arena once (+ the readers' 16-byte pad), then `cap` elements at a time through
+  // one set of per-chunk buffers (stream order keeps a chunk's kernels and downloads ahead of
+  // the next chunk's uploads)
+  size_t chunk = 1u << 20;
+  if (ctx->opts.has(cg::OPT_ECDSA_SIGN_CHUNK))
+    chunk = (size_t)std::min(1 << 20, std::max(1, ctx->opts.i(cg::OPT_ECDSA_SIGN_CHUNK, 1 << 20)));
+  const size_t cap = std::min<size_t>(n, chunk);
+  const size_t invn_words = cg::ecdsa_sign_inv_words((uint32_t)cap, 8), invp_words = cg::ecdsa_sign_inv_words((uint32_t)cap, 10);
+  const bool caller = nonce_mode == CG_ECDSA_NONCE_CALLER;
+  uint8_t *arena_d = nullptr, *stat_d = nullptr, *sig_d = nullptr;
+  uint64_t* off_d = nullptr;
+  uint32_t *len_d = nullptr, *idx_d = nullptr, *k_d = nullptr, *slen_d = nullptr, *st_d = nullptr, *e_d = nullptr,
+           *x_d = nullptr, *invn_d = nullptr, *invp_d = nullptr;
+  cg_status st;
+  if ((st = dalloc(ctx, &arena_d, msg_bytes + 16, "alloc arena")) == CG_OK &&
+      (st = dalloc(ctx, &off_d, cap, "alloc msg_off")) == CG_OK &&
+      (st = dalloc(ctx, &len_d, cap, "alloc msg_len")) == CG_OK &&
+      (!key_index || (st = dalloc(ctx, &idx_d, cap, "alloc key_index")) == CG_OK) &&
+      (!caller || (st = dalloc(ctx, &k_d, 8 * cap, "alloc nonces")) == CG_OK) &&
+      (st = dalloc(ctx, &sig_d, CG_ECDSA_SIG_MAX * cap, "alloc signatures")) == CG_OK &&
+      (st = dalloc(ctx, &slen_d, cap, "alloc signature lengths")) == CG_OK &&
+      (st = dalloc(ctx, &stat_d, cap, "alloc sign status")) == CG_OK &&
+      (st = dalloc(ctx, &st_d, cap, "alloc sign stage status")) == CG_OK &&
+      (st = dalloc(ctx, &e_d, 8 * cap, "alloc digests")) == CG_OK &&
+      (st = dalloc(ctx, &x_d, 10 * cap, "alloc nonce points")) == CG_OK &&
+      (st = dalloc(ctx, &invn_d, invn_words, "alloc scalar inversion")) == CG_OK &&
+      (st = dalloc(ctx, &invp_d, invp_words, "alloc field inversion")) == CG_OK) {
+    hipError_t e = hipSuccess;
+    if (msg_bytes) e = hipMemcpyAsync(arena_d, msg, msg_bytes, hipMemcpyHostToDevice, ctx->stream);
+    cg::EcdsaSignDev d;
+    d.scheme = s->scheme;
+    d.tab = ctx->ecsign_tab[s->scheme == 2 ? 0 : 1];
+    d.key_index = idx_d;
+    d.d = s->d;
+    d.n_keys = (uint32_t)s->n_keys;
+    d.arena = arena_d;
+    d.msg_off = off_d;
+    d.msg_len = len_d;
+    d.nonce_mode = (uint32_t)nonce_mode;
+    d.k_rows = k_d;
+    d.cap = (uint32_t)cap;
+    d.status = st_d;
+    d.ework = e_d;
+    d.xw = x_d;
+    d.invn = invn_d;
+    d.invp = invp_d;
+    d.sig = sig_d;
+    d.sig_len = slen_d;
+    d.status_out = stat_d;
+    const char* span = s->scheme == 2 ? "ecdsa_sign_k1" : "ecdsa_sign_r1";
+    for (size_t base = 0; base < n && e == hipSuccess; base += cap) {
+      const size_t m = std::min(cap, n - base);
+      e = hipMemcpyAsync(off_d, msg_off + base, m * 8, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(len_d, msg_len + base, m * 4, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess && key_index)
+        e = hipMemcpyAsync(idx_d, key_index + base, m * 4, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess && caller)
+        e = hipMemcpyAsync(k_d, k_be + 32 * base, m * 32, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess) {
+        Timed t(ctx, span, m);
+        e = cg::launch_ecdsa_sign_stage(d, (uint32_t)m, 0, ctx->stream);
+      }
+      if (e == hipSuccess) {
+        Timed t(ctx, "ecdsa_sign_inv", m);
+        e = cg::launch_ecdsa_sign_stage(d, (uint32_t)m, 1, ctx->stream);
+      }
+      if (e == hipSuccess) {
+        Timed t(ctx, span, 0);  // (the elements were counted with the first half)
+        e = cg::launch_ecdsa_sign_stage(d, (uint32_t)m, 2, ctx->stream);
+      }
+      if (e == hipSuccess) {
+        if (sig_stride == CG_ECDSA_SIG_MAX)
+          e = hipMemcpyAsync(sig_out + sig_stride * base, sig_d, CG_ECDSA_SIG_MAX * m, hipMemcpyDeviceToHost,
+                             ctx->stream);
+        else
+          e = hipMemcpy2DAsync(sig_out + sig_stride * base, sig_stride, sig_d, CG_ECDSA_SIG_MAX, CG_ECDSA_SIG_MAX, m,
+                               hipMemcpyDeviceToHost, ctx->stream);
+      }
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(sig_len_out + base, slen_d, m * 4, hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess && status_out)
+        e = hipMemcpyAsync(status_out + base, stat_d, m, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) st = hip_fail(ctx, e, "ecdsa sign");
+    if (st == CG_OK && sig_stride > CG_ECDSA_SIG_MAX)  // a row's bytes past the device's 72 are zero too
+      for (size_t i = 0; i < n; ++i)
+        std::memset(sig_out + sig_stride * i + CG_ECDSA_SIG_MAX, 0, sig_stride - CG_ECDSA_SIG_MAX);
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  // the blocks that held k (the caller's rows; k R in the inversion leaves), k^-1, products
+  // of them and e are zeroed before they return to the cache
+  const std::pair<void*, size_t> secret[] = {{k_d, 32 * cap}, {e_d, 32 * cap}, {x_d, 40 * cap},
+                                             {invn_d, invn_words * 4}, {invp_d, invp_words * 4}};
+  for (const auto& b : secret)
+    if (b.first) (void)hipMemsetAsync(b.first, 0, b.second, ctx->stream);
+  (void)hipStreamSynchronize(ctx->stream);
+  for (const void* p : {(const void*)k_d, (const void*)e_d, (const void*)x_d, (const void*)invn_d,
+                        (const void*)invp_d, (const void*)arena_d, (const void*)off_d, (const void*)len_d,
+                        (const void*)idx_d, (const void*)sig_d, (const void*)slen_d, (const void*)stat_d,
+                        (const void*)st_d})
     dfree(ctx, p);
   collect_timings(ctx);
   return st;

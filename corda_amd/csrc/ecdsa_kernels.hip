@@ -11,6 +11,7 @@
 //                     windows); secp256k1: u1 G + k1 Q + k2 phi(Q) over ~129 bits
 //                     (G and 2^128 G tables); then the projective x check
 //   cg_ecdsa_gtab_build<C>  the shared generator tables (context creation)
+// K11, batch signing (cg_ecdsa_sign.h): cg_ecdsa_sign_front / _back, _keyexp, _signtab_build, below.
 //
 // Device layout (cap = subset size, scap = scratch chunk):
 //   q[w*cap+i] (16 words: the 64-byte big-endian X||Y as staged little-endian
@@ -26,6 +27,7 @@
 
 #include "cg_ecdsa.h"
 #include "cg_ecdsa_api.h"
+#include "cg_ecdsa_sign.h"
 #include "cg_kernels.h"
 
 using namespace cg;
@@ -92,6 +94,7 @@ CG_DEV void q_load(const uint32_t* e, f26& X, f26& Y) {
   }
 }
 constexpr int kDigitWordsEc = 27;
+constexpr int kEcSigRow = 72;  // signing: one DER row (CG_ECDSA_SIG_MAX), zero past the signature
 
 CG_DEV uint32_t wave_max_u32(uint32_t v) {
   CG_UNROLL for (int o = 32; o >= 1; o >>= 1) {
@@ -622,6 +625,139 @@ hipError_t launch_msm(const EcdsaBatch& b, EcdsaConsts* cc, uint32_t base, uint3
   return hipGetLastError();
 }
 
+
+// ------------------------------------------------------------------ signing (K11)
+// cg_ecdsa_sign.h, DESIGN.md §3.8.  One lane per element, three stages per chunk:
+//   cg_ecdsa_sign_front<C>  e = SHA-256(M), the nonce (RFC 6979 or the caller's row), R = k G
+//                           over the per-window tables; leaves of the two inversions:
+//                           k R mod n and Z(R) (ones for lanes already decided)
+//   cg_inv_up / cg_inv_roots / cg_inv_down   the chunk's two product trees (as in the verifier)
+//   cg_ecdsa_sign_back<C>   r = X / Z^2 mod n, s = k^-1 (e + d r) mod n, strict DER -> a
+//                           72-byte row (zero past the signature), its length, the outcome
+//   cg_ecdsa_sign_keyexp<C> Q = d G (signer creation); cg_ecdsa_signtab_build<C> the tables
+// Signer keys: d[w * n_keys + j] (8 LE limbs).  Chunk scratch (cap elements): status[i],
+// ework[w * cap + i] (e mod n), xw[w * cap + i] (X of R, 10 limbs), the two inversion
+// buffers (inv_layout).
+CG_DEV void sign_tab_load(const uint32_t* __restrict__ tab, uint32_t j, uint32_t a, jpt& p) {
+  // 80 bytes of one 128-byte line, five 16-byte loads (Z implied: ec_add<C, true> never reads it)
+  const int4* g = reinterpret_cast<const int4*>(tab + (size_t)ecdsa_sign_tab_index(j, a) * kSignEntryWords);
+  int32_t v[20];
+  CG_UNROLL for (int q = 0; q < 5; ++q) {
+    const int4 x = g[q];
+    v[4 * q] = x.x;
+    v[4 * q + 1] = x.y;
+    v[4 * q + 2] = x.z;
+    v[4 * q + 3] = x.w;
+  }
+  CG_UNROLL for (int w = 0; w < 10; ++w) {
+    p.X.v[w] = v[w];
+    p.Y.v[w] = v[10 + w];
+  }
+  p.inf = 0;
+}
+
+// Entry (j, a) = affine a 2^(kSignWin j) G; a = 0 entries (never read) are zero.  One lane per entry.
+template <class C>
+__global__ __launch_bounds__(256) void cg_ecdsa_signtab_build(uint32_t* __restrict__ out) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= kSignTabEntries) return;
+  const uint32_t j = e / kSignTabStride, a = e % kSignTabStride;
+  f26 x, y;
+  CG_UNROLL for (int w = 0; w < 10; ++w) x.v[w] = y.v[w] = 0;
+  if (a) ecdsa_sign_tab_entry<C>(j, a, x, y);
+  CG_UNROLL for (int w = 0; w < 10; ++w) {
+    out[(size_t)e * kSignEntryWords + w] = (uint32_t)x.v[w];
+    out[(size_t)e * kSignEntryWords + 10 + w] = (uint32_t)y.v[w];
+  }
+}
+
+// Q = d G per key -> pub[16 j ..]: the 64-byte verify key form X || Y (big-endian).
+template <class C>
+__global__ __launch_bounds__(256) void cg_ecdsa_sign_keyexp(const uint32_t* __restrict__ d_g, uint32_t n_keys,
+                                                            const uint32_t* __restrict__ tab,
+                                                            uint32_t* __restrict__ pub) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_keys) return;
+  uint32_t d[8], qx[8], qy[8];
+  CG_UNROLL for (int w = 0; w < 8; ++w) d[w] = d_g[(size_t)w * n_keys + j];
+  ecdsa_sign_pubkey<C>(qx, qy, d, [&](uint32_t t, uint32_t a, jpt& p) CG_LINLINE { sign_tab_load(tab, t, a, p); });
+  CG_UNROLL for (int w = 0; w < 8; ++w) {
+    pub[(size_t)16 * j + w] = bswap32_(qx[7 - w]);
+    pub[(size_t)16 * j + 8 + w] = bswap32_(qy[7 - w]);
+  }
+}
+
+template <class C>
+__global__ __launch_bounds__(256) void cg_ecdsa_sign_front(
+    const uint32_t* __restrict__ key_index, const uint32_t* __restrict__ d_g, uint32_t n_keys,
+    const uint8_t* __restrict__ arena, const uint64_t* __restrict__ msg_off, const uint32_t* __restrict__ msg_len,
+    uint32_t nonce_mode, const uint32_t* __restrict__ k_rows, const uint32_t* __restrict__ tab, uint32_t n,
+    uint32_t cap, uint32_t* __restrict__ status, uint32_t* __restrict__ ework, uint32_t* __restrict__ xw,
+    uint32_t* __restrict__ leaf_n, uint32_t* __restrict__ leaf_p) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t j = key_index ? key_index[i] : 0u;  // (< n_keys: checked on the host before the launch)
+  uint32_t d[8], kc[8], e[8], k[8], a[8];
+  CG_UNROLL for (int w = 0; w < 8; ++w) {
+    d[w] = d_g[(size_t)w * n_keys + j];
+    kc[w] = nonce_mode == ECNONCE_CALLER ? bswap32_(k_rows[(size_t)8 * i + 7 - w]) : 0u;
+  }
+  jpt R;
+  const uint32_t len = msg_len[i];
+  const uint32_t st = ecdsa_sign_front<C>(d, arena + (len ? msg_off[i] : 0), len, nonce_mode, kc, e, k, R,
+                                          [&](uint32_t t, uint32_t v, jpt& p) CG_LINLINE { sign_tab_load(tab, t, v, p); });
+  status[i] = st;
+  if (st != ECSIGN_OK) {
+    uint32_t o[10];
+    InvN<C>::one(a);
+    gl_put<8>(leaf_n + (size_t)i * 8, a);
+    InvP<C>::one(o);
+    gl_put<10>(leaf_p + (size_t)i * 10, o);
+    return;
+  }
+  uint32_t r2[8], z[10];
+  mn_r2<C>(r2);
+  mn_mul<C>(a, k, r2);
+  gl_put<8>(leaf_n + (size_t)i * 8, a);
+  CG_UNROLL for (int w = 0; w < 10; ++w) z[w] = (uint32_t)R.Z.v[w];
+  gl_put<10>(leaf_p + (size_t)i * 10, z);
+  CG_UNROLL for (int w = 0; w < 8; ++w) ework[(size_t)w * cap + i] = e[w];
+  CG_UNROLL for (int w = 0; w < 10; ++w) xw[(size_t)w * cap + i] = (uint32_t)R.X.v[w];
+}
+
+template <class C>
+__global__ __launch_bounds__(256) void cg_ecdsa_sign_back(
+    const uint32_t* __restrict__ key_index, const uint32_t* __restrict__ d_g, uint32_t n_keys, uint32_t n, uint32_t cap,
+    const uint32_t* __restrict__ status, const uint32_t* __restrict__ ework, const uint32_t* __restrict__ xw,
+    const uint32_t* __restrict__ leaf_n, const uint32_t* __restrict__ leaf_p, uint8_t* __restrict__ sig,
+    uint32_t* __restrict__ sig_len, uint8_t* __restrict__ status_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint8_t* row = sig + (size_t)kEcSigRow * i;
+  CG_UNROLL for (int q = 0; q < kEcSigRow / 8; ++q) reinterpret_cast<uint2*>(row)[q] = make_uint2(0u, 0u);
+  uint32_t st = status[i], len = 0;
+  if (st == ECSIGN_OK) {
+    const uint32_t j = key_index ? key_index[i] : 0u;
+    uint32_t d[8], e[8], kinv[8], zw[10], r[8], s[8];
+    f26 X, zi;
+    CG_UNROLL for (int w = 0; w < 8; ++w) {
+      d[w] = d_g[(size_t)w * n_keys + j];
+      e[w] = ework[(size_t)w * cap + i];
+    }
+    gl_get<8>(kinv, leaf_n + (size_t)i * 8);
+    gl_get<10>(zw, leaf_p + (size_t)i * 10);
+    CG_UNROLL for (int w = 0; w < 10; ++w) {
+      X.v[w] = (int32_t)xw[(size_t)w * cap + i];
+      zi.v[w] = (int32_t)zw[w];
+    }
+    st = ecdsa_sign_finish<C>(d, e, X, zi, kinv, r, s);
+    // the row was zeroed above by this lane: stores of one lane to one address stay in order
+    if (st == ECSIGN_OK) len = ecdsa_der_encode(r, s, [&](uint32_t pos, uint32_t b) CG_LINLINE { row[pos] = (uint8_t)b; });
+  }
+  sig_len[i] = len;
+  status_out[i] = (uint8_t)st;
+}
+
 }  // namespace
 
 namespace cg {
@@ -707,6 +843,65 @@ hipError_t ecdsa_launch_msm(const EcdsaBatch& b, EcdsaConsts* c, uint32_t base, 
   if (cnt == 0) return hipSuccess;
   return b.scheme == 2 ? launch_msm<CurveK1>(b, c, base, cnt, verdict, s)
                        : launch_msm<CurveR1>(b, c, base, cnt, verdict, s);
+}
+
+// ------------------------------------------------------------------ signing (K11)
+size_t ecdsa_sign_tab_words() { return (size_t)kSignTabEntries * kSignEntryWords; }
+size_t ecdsa_sign_inv_words(uint32_t cap, int words) { return inv_layout(cap, words, nullptr, nullptr, nullptr); }
+
+hipError_t launch_ecdsa_signtab_build(int scheme, uint32_t* tab, hipStream_t s) {
+  if (scheme == 2)
+    hipLaunchKernelGGL(cg_ecdsa_signtab_build<CurveK1>, grid_for(kSignTabEntries), dim3(256), 0, s, tab);
+  else
+    hipLaunchKernelGGL(cg_ecdsa_signtab_build<CurveR1>, grid_for(kSignTabEntries), dim3(256), 0, s, tab);
+  return hipGetLastError();
+}
+
+hipError_t launch_ecdsa_sign_keyexp(int scheme, const uint32_t* tab, const uint32_t* d, uint32_t n_keys, uint32_t* pub,
+                                    hipStream_t s) {
+  if (n_keys == 0) return hipSuccess;
+  if (scheme == 2)
+    hipLaunchKernelGGL(cg_ecdsa_sign_keyexp<CurveK1>, grid_for(n_keys), dim3(256), 0, s, d, n_keys, tab, pub);
+  else
+    hipLaunchKernelGGL(cg_ecdsa_sign_keyexp<CurveR1>, grid_for(n_keys), dim3(256), 0, s, d, n_keys, tab, pub);
+  return hipGetLastError();
+}
+
+namespace {
+
+template <class C>
+hipError_t sign_stage(const EcdsaSignDev& d, uint32_t n, int stage, hipStream_t s) {
+  size_t vn[kInvMaxLevels + 1], tn[kInvMaxLevels], vp[kInvMaxLevels + 1], tp[kInvMaxLevels];
+  int ln = 0, lp = 0;
+  if (n > d.cap || inv_layout(n, 8, vn, tn, &ln) > inv_layout(d.cap, 8, nullptr, nullptr, nullptr) ||
+      inv_layout(n, 10, vp, tp, &lp) > inv_layout(d.cap, 10, nullptr, nullptr, nullptr) || ln > kInvMaxLevels ||
+      lp > kInvMaxLevels)
+    return hipErrorInvalidValue;
+  if (stage == 0) {
+    hipLaunchKernelGGL(cg_ecdsa_sign_front<C>, grid_for(n), dim3(256), 0, s, d.key_index, d.d, d.n_keys, d.arena,
+                       d.msg_off, d.msg_len, d.nonce_mode, d.k_rows, d.tab, n, d.cap, d.status, d.ework, d.xw,
+                       d.invn + vn[0], d.invp + vp[0]);
+  } else if (stage == 1) {
+    uint32_t m[kInvMaxLevels + 1];  // both trees have n leaves
+    m[0] = n;
+    for (int l = 0; l < ln; ++l) m[l + 1] = (m[l] + 255) / 256;
+    launch_inv_up<InvN<C>>(d.invn, vn, tn, m, ln, s);
+    launch_inv_up<InvP<C>>(d.invp, vp, tp, m, lp, s);
+    hipLaunchKernelGGL(cg_inv_roots<C>, dim3(1), dim3(128), 0, s, d.invn + vn[ln], d.invp + vp[lp]);
+    launch_inv_down<InvN<C>>(d.invn, vn, tn, m, ln, s);
+    launch_inv_down<InvP<C>>(d.invp, vp, tp, m, lp, s);
+  } else {
+    hipLaunchKernelGGL(cg_ecdsa_sign_back<C>, grid_for(n), dim3(256), 0, s, d.key_index, d.d, d.n_keys, n, d.cap,
+                       d.status, d.ework, d.xw, d.invn + vn[0], d.invp + vp[0], d.sig, d.sig_len, d.status_out);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_ecdsa_sign_stage(const EcdsaSignDev& d, uint32_t n, int stage, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  return d.scheme == 2 ? sign_stage<CurveK1>(d, n, stage, s) : sign_stage<CurveR1>(d, n, stage, s);
 }
 
 }  // namespace cg

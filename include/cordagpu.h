@@ -73,9 +73,9 @@
 extern "C" {
 #endif
 
-/* The signing entry points (cg_signer_*, cg_sign_batch) and the FilteredTransaction builder
- * (cg_ftx_build_layout, cg_ftx_build_batch) are purely additive: no existing signature or
- * layout changed, so the version stays 4. */
+/* The signing entry points (cg_signer_*, cg_sign_batch, cg_ecdsa_signer_*, cg_ecdsa_sign_batch)
+ * and the FilteredTransaction builder (cg_ftx_build_layout, cg_ftx_build_batch) are purely
+ * additive: no existing signature or layout changed, so the version stays 4. */
 #define CG_ABI_VERSION 4  /* 4: cg_set_option; the CORDA_AMD_* knobs read once, at cg_open */
 
 typedef int32_t cg_status;
@@ -331,8 +331,7 @@ cg_status cg_composite_eval_batch(cg_ctx* ctx, size_t n_q, const uint32_t* prog_
  * EdDSAEngine.sign: deterministic, RFC 8032) — what a notary does to every transaction id
  * it accepts: NotaryFlow.kt:125-126 service.sign(txId.bytes) -> NotaryService.kt:75-77
  * keyManagementService.sign -> Crypto.doSign.  The 64 signature bytes equal the JVM's.
- * ECDSA signing is not offered: BC 1.57 draws its nonce from SecureRandom, so there is no
- * byte-exact target.
+ * ECDSA keys sign through cg_ecdsa_sign_batch (below).
  *
  * A cg_signer holds n_keys private keys on the device, expanded once.  seeds: 32 bytes per
  * key, the wire form of an EdDSAPrivateKey (Ed25519PrivateKeySerializer writes obj.seed,
@@ -366,6 +365,68 @@ cg_status cg_sign_batch(cg_ctx* ctx, const cg_signer* signer, size_t n, const ui
                         uint8_t* sig_out, uint8_t* status_out);
 
 /*
+ * ECDSA batch signing (ECDSA_SECP256K1_SHA256 = scheme 2, ECDSA_SECP256R1_SHA256 = scheme 3):
+ * the same Crypto.doSign loop for an EC private key (DSABase.engineSign -> BC 1.57
+ * ECDSASigner.generateSignature -> StdDSAEncoder.encode).  generateSignature is a pure
+ * function of (d, e, k): e = SHA-256(M) as a 256-bit integer, r = x(k G) mod n,
+ * s = k^-1 (e + d r) mod n, encoded as minimal DER 30 L 02 Lr r 02 Ls s (8..72 bytes, no
+ * low-S normalisation); it draws k again when k is outside [1, n-1], r = 0 or s = 0.  BC
+ * takes k from SecureRandom, so the byte-exact target exists once the nonce is an input:
+ *   CG_ECDSA_NONCE_CALLER   k_be[32 i ..]: element i's nonce, 32 big-endian bytes, drawn by the
+ *                           caller as RandomDSAKCalculator.nextK does (BigInteger(256, random)
+ *                           until it lies in [1, n-1]).  The signature equals BC's for that k.
+ *                           A k of 0 or >= n is never reduced: CG_SIGN_NONCE_INVALID.
+ *   CG_ECDSA_NONCE_RFC6979  k derived on the device by RFC 6979 section 3.2 (HMAC-SHA-256,
+ *                           x = d, h = e mod n): deterministic, no randomness needed; k_be
+ *                           is not read.  Any BC or other verifier accepts the result.
+ *
+ * A cg_ecdsa_signer holds n_keys private scalars of one curve on the device.  d_be: 32
+ * big-endian bytes per key, 0 < d < n (else CG_E_INVALID_ARGUMENT naming the key index).  The
+ * first signer of a curve builds that curve's fixed-base tables on the device (kept until
+ * cg_close; a context that never signs allocates none).  The library keeps no host copy of
+ * the scalars; the signer's device arrays are zeroed at destroy, and the per-call scratch
+ * that held k, k^-1 or values derived from d is zeroed before its memory is reused.
+ * cg_last_error never contains key or nonce bytes.  Table lookups on the device are indexed
+ * by secret digits and the batched inversion's root is inverted in variable time (not
+ * constant-time): run one signing process per GPU.
+ * cg_ecdsa_signer_public_keys: Q = d G per key as 64 bytes X || Y, the key form
+ * cg_verify_batch takes for schemes 2 and 3.
+ *
+ * cg_ecdsa_sign_batch: element i signs msg[msg_off[i] .. msg_off[i] + msg_len[i]) with key
+ * key_index[i] (NULL: key 0).  sig_out / sig_stride (>= CG_ECDSA_SIG_MAX) / sig_len_out are
+ * exactly the sig / sig_stride / sig_len of cg_verify_batch; the bytes of a row past its
+ * signature are zero.  status_out (optional, n bytes), highest precedence first:
+ *   CG_SIGN_EMPTY          empty clear data (Crypto.kt:397)
+ *   CG_SIGN_NONCE_INVALID  caller mode: k = 0 or k >= n (nextK would draw again)
+ *   CG_SIGN_DEGENERATE     r = 0 or s = 0 (generateSignature would draw again).  In RFC 6979
+ *                          mode this needs a key chosen against the message's nonce; it is
+ *                          unreachable for an honestly generated key.
+ *   CG_SIGN_OK             signed
+ * A non-OK element has sig_len_out 0 and a zero row; the call still returns CG_OK.
+ * CG_E_INVALID_ARGUMENT before any copy or launch (the message names the element or key):
+ * a scheme other than 2 or 3, d = 0 or >= n, key_index[i] >= n_keys, a message outside the
+ * arena, sig_stride < CG_ECDSA_SIG_MAX, an unknown nonce mode, k_be NULL in caller mode, a
+ * required pointer NULL.  Batches run CORDA_AMD_ECDSA_SIGN_CHUNK (default and at most 2^20)
+ * elements at a time.
+ * Profiling spans: "ecdsa_keyexp" (cg_ecdsa_signer_create; "ecdsa_signtab" the table build of
+ * a curve's first signer), "ecdsa_sign_k1" / "ecdsa_sign_r1" (hash, nonce, k G; r, s, DER),
+ * "ecdsa_sign_inv" (the two batched inversions between them).
+ */
+typedef struct cg_ecdsa_signer cg_ecdsa_signer;
+enum { CG_ECDSA_NONCE_RFC6979 = 0, CG_ECDSA_NONCE_CALLER = 1 };
+enum { CG_SIGN_NONCE_INVALID = 2, CG_SIGN_DEGENERATE = 3 };
+#define CG_ECDSA_SIG_MAX 72
+cg_status cg_ecdsa_signer_create(cg_ctx* ctx, int scheme, size_t n_keys, const uint8_t* d_be, cg_ecdsa_signer** out);
+size_t cg_ecdsa_signer_size(const cg_ecdsa_signer* signer);
+int cg_ecdsa_signer_scheme(const cg_ecdsa_signer* signer);
+cg_status cg_ecdsa_signer_public_keys(cg_ctx* ctx, const cg_ecdsa_signer* signer, uint8_t* xy_out);
+void cg_ecdsa_signer_destroy(cg_ctx* ctx, cg_ecdsa_signer* signer);
+cg_status cg_ecdsa_sign_batch(cg_ctx* ctx, const cg_ecdsa_signer* signer, size_t n, const uint32_t* key_index,
+                              const uint8_t* msg, size_t msg_bytes, const uint64_t* msg_off, const uint32_t* msg_len,
+                              int nonce_mode, const uint8_t* k_be, uint8_t* sig_out, size_t sig_stride,
+                              uint32_t* sig_len_out, uint8_t* status_out);
+
+/*
  * Host-memory registration (optional).  Page-locks [ptr, ptr + bytes) for the
  * device so later uploads from that range run at full PCIe DMA rate instead of
  * through the runtime's pageable staging copy.  Meant for buffers a caller reuses
@@ -383,7 +444,8 @@ cg_status cg_release_cached(cg_ctx* ctx);
  * profiling is enabled.  Names: "ed25519_hash", "ed25519_points", "ed25519_msm",
  * "ecdsa_k1_prep", "ecdsa_k1_msm", "ecdsa_r1_prep", "ecdsa_r1_msm", "der_parse",
  * "merkle_leaf", "merkle_tree", "pmt_eval", "composite_eval", "stage", "ed25519_keyexp",
- * "ed25519_sign", "pmt_nonce", "pmt_build".
+ * "ed25519_sign", "pmt_nonce", "pmt_build", "ecdsa_keyexp", "ecdsa_sign_k1", "ecdsa_sign_r1",
+ * "ecdsa_sign_inv", "ecdsa_signtab".
  * enable: 0 off, 1 every span, 2 only the "call" span of each cg_verify_batch (its
  * GPU time from entry to the verdict download; two events per call).
  */

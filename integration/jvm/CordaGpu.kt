@@ -20,8 +20,11 @@ import net.corda.core.transactions.WireTransaction
 import java.nio.ByteBuffer
 import java.nio.ByteOrder
 import java.security.InvalidKeyException
+import java.math.BigInteger
 import java.security.PublicKey
+import java.security.SecureRandom
 import java.security.SignatureException
+import java.security.interfaces.ECPrivateKey
 import java.security.interfaces.ECPublicKey
 import net.corda.core.crypto.SecureHash
 import net.i2p.crypto.eddsa.EdDSAPrivateKey
@@ -210,6 +213,86 @@ class CordaGpu(device: Int = 0) : AutoCloseable {
         override fun close() = nativeSignerDestroy(handle, s)
     }
 
+    /**
+     * EC private keys of one curve held on the device (cg_ecdsa_signer_create).  scheme: 2
+     * (ECDSA_SECP256K1_SHA256) or 3 (ECDSA_SECP256R1_SHA256).  A key goes over as the 32 big-endian bytes of
+     * ECPrivateKey.s; the direct buffer that carried them is zeroed before the constructor returns.
+     */
+    inner class EcdsaSigner(val scheme: Int, privateKeys: List<ECPrivateKey>) : AutoCloseable {
+        val n = privateKeys.size
+        private val order: BigInteger = privateKeys.firstOrNull()?.params?.order ?: BigInteger.ONE
+        private val s: Long
+        init {
+            val d = direct(32 * n)
+            privateKeys.forEach { d.put(be32(it.s)) }
+            try {
+                s = nativeEcdsaSignerCreate(handle, scheme, n, d)
+            } finally {
+                for (i in 0 until 32 * n) d.put(i, 0)
+            }
+            check(s > 0L) { "libcordagpu error $s: ${nativeLastError(handle)}" }
+        }
+
+        /** Q = d G of every key as 64 bytes X || Y, the key form nativeVerify takes. */
+        fun publicKeys(): List<ByteArray> {
+            val out = direct(64 * n)
+            check(nativeEcdsaSignerPublicKeys(handle, s, out))
+            return (0 until n).map { j -> ByteArray(64).also { out.position(64 * j); out.get(it) } }
+        }
+
+        /**
+         * A loop of [Crypto.doSign] for EC keys in one device call.  BC 1.57's ECDSASigner.generateSignature is a
+         * pure function of (d, e, k): with secureRandom given, the nonces are drawn here exactly as
+         * RandomDSAKCalculator.nextK draws them — BigInteger(256, secureRandom) until it lies in [1, n-1] — so the
+         * DER bytes are the ones BC would have produced from those draws; an element whose nonce gives r = 0 or
+         * s = 0 is drawn and signed again, as generateSignature's loop does.  secureRandom = null: RFC 6979 nonces
+         * derived on the device (deterministic).  Throws IllegalArgumentException for the lowest empty element
+         * (Crypto.kt:397).
+         */
+        fun sign(clearData: List<ByteArray>, keyIndex: IntArray? = null, secureRandom: SecureRandom? = null): List<ByteArray> {
+            val m = clearData.size
+            val msg = direct(clearData.sumBy { it.size }); val msgOff = direct(8 * m); val msgLen = direct(4 * m)
+            val idx = keyIndex?.let { k -> direct(4 * m).also { b -> k.forEachIndexed { i, v -> b.putInt(4 * i, v) } } }
+            var off = 0L
+            for (i in 0 until m) {
+                msgOff.putLong(8 * i, off); msgLen.putInt(4 * i, clearData[i].size)
+                msg.position(off.toInt()); msg.put(clearData[i]); off += clearData[i].size
+            }
+            val kBe = secureRandom?.let { rnd -> direct(32 * m).also { b -> for (i in 0 until m) b.put(be32(nextK(rnd))) } }
+            val sig = direct(ECDSA_SIG_MAX * m); val sigLen = direct(4 * m); val status = direct(m)
+            val mode = if (secureRandom == null) ECDSA_NONCE_RFC6979 else ECDSA_NONCE_CALLER
+            try {
+                check(ecdsaSignBatch(handle, s, m, idx, msg, msgOff, msgLen, mode, kBe, sig, ECDSA_SIG_MAX, sigLen, status))
+            } finally {
+                kBe?.let { b -> for (i in 0 until 32 * m) b.put(i, 0) }
+            }
+            val out = arrayOfNulls<ByteArray>(m)
+            for (i in 0 until m) {
+                val st = status.get(i).toInt()
+                require(st != SIGN_EMPTY) { "Signing of an empty array is not permitted!" }
+                if (st == SIGN_OK) out[i] = ByteArray(sigLen.getInt(4 * i)).also { sig.position(ECDSA_SIG_MAX * i); sig.get(it) }
+            }
+            // r = 0 or s = 0 (probability ~2^-255 per draw): generateSignature draws k again
+            val again = (0 until m).filter { out[it] == null }
+            if (again.isNotEmpty()) {
+                check(secureRandom != null) { "degenerate RFC 6979 signature: the key was chosen against the message" }
+                val redo = sign(again.map { clearData[it] }, keyIndex?.let { k -> IntArray(again.size) { j -> k[again[j]] } }, secureRandom)
+                again.forEachIndexed { j, i -> out[i] = redo[j] }
+            }
+            return out.map { it!! }
+        }
+
+        /** RandomDSAKCalculator.nextK: BigInteger(qBitLength, random) until 1 <= k < n. */
+        private fun nextK(rnd: SecureRandom): BigInteger {
+            while (true) {
+                val k = BigInteger(256, rnd)
+                if (k.signum() > 0 && k < order) return k
+            }
+        }
+
+        override fun close() = nativeEcdsaSignerDestroy(handle, s)
+    }
+
     /** Batch form of [Crypto.doSign]: element i signed with privateKeys[i] (Ed25519 keys only). */
     fun doSignBatch(privateKeys: List<EdDSAPrivateKey>, clearData: List<ByteArray>): List<ByteArray> {
         require(privateKeys.size == clearData.size) { "privateKeys and clearData differ in length" }
@@ -225,6 +308,18 @@ class CordaGpu(device: Int = 0) : AutoCloseable {
         const val PK_STRIDE = 64
         const val CG_E_MERKLE_EMPTY = -5
         const val SIGN_OK = 0; const val SIGN_EMPTY = 1  // cg_sign_batch status bytes
+        const val SIGN_NONCE_INVALID = 2; const val SIGN_DEGENERATE = 3  // cg_ecdsa_sign_batch: further status bytes
+        const val ECDSA_NONCE_RFC6979 = 0; const val ECDSA_NONCE_CALLER = 1
+        const val ECDSA_SIG_MAX = 72  // CG_ECDSA_SIG_MAX: the longest DER signature, the least sig_stride
+
+        /** v as exactly 32 big-endian bytes (0 <= v < 2^256). */
+        fun be32(v: BigInteger): ByteArray {
+            val raw = v.toByteArray()  // minimal two's complement: at most one leading zero byte above 32
+            val out = ByteArray(32)
+            val take = minOf(raw.size, 32)
+            System.arraycopy(raw, raw.size - take, out, 32 - take, take)
+            return out
+        }
         init { System.loadLibrary("cordagpu_jni") }
 
         @JvmStatic external fun nativeOpen(device: Int): Long
@@ -270,6 +365,13 @@ class CordaGpu(device: Int = 0) : AutoCloseable {
         @JvmStatic external fun signBatch(handle: Long, signer: Long, n: Int, keyIndex: ByteBuffer?, msg: ByteBuffer,
                                           msgOff: ByteBuffer, msgLen: ByteBuffer, sigOut: ByteBuffer,
                                           status: ByteBuffer?): Int
+        @JvmStatic external fun nativeEcdsaSignerCreate(handle: Long, scheme: Int, nKeys: Int, dBe: ByteBuffer): Long
+        @JvmStatic external fun nativeEcdsaSignerPublicKeys(handle: Long, signer: Long, xyOut: ByteBuffer): Int
+        @JvmStatic external fun nativeEcdsaSignerDestroy(handle: Long, signer: Long)
+        @JvmStatic external fun ecdsaSignBatch(handle: Long, signer: Long, n: Int, keyIndex: ByteBuffer?, msg: ByteBuffer,
+                                               msgOff: ByteBuffer, msgLen: ByteBuffer, nonceMode: Int, kBe: ByteBuffer?,
+                                               sigOut: ByteBuffer, sigStride: Int, sigLenOut: ByteBuffer,
+                                               status: ByteBuffer?): Int
         @JvmStatic external fun nativeCompositeEval(handle: Long, nQ: Int, progStart: ByteBuffer, prog: ByteBuffer,
                                                     nSig: Int, sigStart: ByteBuffer, verdicts: ByteBuffer?,
                                                     out: ByteBuffer): Int

@@ -11,6 +11,9 @@
  *   nativeSignerCreate/...  cg_signer_*              Ed25519 private keys expanded once on the device
  *   signBatch               cg_sign_batch            a loop of Crypto.doSign (Crypto.kt:394-401): the notary's
  *                                                    service.sign(txId.bytes) (NotaryFlow.kt:125-126)
+ *   nativeEcdsaSigner...    cg_ecdsa_signer_*        EC private scalars (secp256k1 / secp256r1) held on the device
+ *   ecdsaSignBatch          cg_ecdsa_sign_batch      the same doSign loop for EC keys: BC's generateSignature
+ *                                                    with the nonce supplied (or RFC 6979 on the device)
  *   nativeFtxBuildLayout    cg_ftx_build_layout      output sizes of the next one (host only)
  *   buildFilteredBatch      cg_ftx_build_batch       a loop of wtx.buildFilteredTransaction (NotaryFlow.kt:72)
  *
@@ -208,4 +211,49 @@ JNIEXPORT jint JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_buildFilteredBatc
   return cg_ftx_build_batch(h > 0 ? CTX(h) : 0, m, BUF(arena), CAP(arena), BUF(comp_off), BUF(comp_len),
                             BUF(comp_start), BUF(salts), BUF(include), fcap, ncap, BUF(fcomp_start), BUF(fcomp_index),
                             BUF(nonces), BUF(node_start), BUF(node_kind), BUF(node_hash), BUF(roots));
+}
+
+/* ECDSA signing (cg_ecdsa_signer_*, cg_ecdsa_sign_batch: Crypto.doSign for an EC private key).
+ * The signer handle is a cg_ecdsa_signer* as a jlong (a failed create returns the negative
+ * cg_status); d: a direct buffer of 32 big-endian bytes per key, which the caller overwrites
+ * after the call. */
+JNIEXPORT jlong JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_nativeEcdsaSignerCreate(JNIEnv* env, jclass cls,
+                                                                                        jlong h, jint scheme,
+                                                                                        jint n_keys, jobject d) {
+  cg_ecdsa_signer* s = 0;
+  if (n_keys < 0 || CAP(d) < (size_t)n_keys * 32) return CG_E_INVALID_ARGUMENT;
+  const cg_status st = cg_ecdsa_signer_create(h > 0 ? CTX(h) : 0, scheme, (size_t)n_keys, BUF(d), &s);
+  return st == CG_OK ? (jlong)(intptr_t)s : (jlong)st;
+}
+
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_nativeEcdsaSignerPublicKeys(JNIEnv* env, jclass cls,
+                                                                                           jlong h, jlong signer,
+                                                                                           jobject xy_out) {
+  if (signer <= 0) return CG_E_INVALID_ARGUMENT;
+  const cg_ecdsa_signer* s = (const cg_ecdsa_signer*)(intptr_t)signer;
+  if (CAP(xy_out) < cg_ecdsa_signer_size(s) * 64) return CG_E_INVALID_ARGUMENT;
+  return cg_ecdsa_signer_public_keys(h > 0 ? CTX(h) : 0, s, BUF(xy_out));
+}
+
+JNIEXPORT void JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_nativeEcdsaSignerDestroy(JNIEnv* env, jclass cls,
+                                                                                        jlong h, jlong signer) {
+  if (h > 0 && signer > 0) cg_ecdsa_signer_destroy(CTX(h), (cg_ecdsa_signer*)(intptr_t)signer);
+}
+
+/* One call per batch: key_index (null: key 0), the message arena with its offsets and lengths,
+ * k_be (n * 32 bytes; null in RFC 6979 mode), sig_out (n * sig_stride bytes), sig_len_out
+ * (n * 4 bytes) and status (null, or n bytes) are direct buffers. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_gpu_CordaGpu_ecdsaSignBatch(
+    JNIEnv* env, jclass cls, jlong h, jlong signer, jint n, jobject key_index, jobject msg, jobject msg_off,
+    jobject msg_len, jint nonce_mode, jobject k_be, jobject sig_out, jint sig_stride, jobject sig_len_out,
+    jobject status) {
+  if (signer <= 0 || n < 0 || sig_stride < 0) return CG_E_INVALID_ARGUMENT;
+  const size_t m = (size_t)n;
+  if ((key_index && CAP(key_index) < 4 * m) || CAP(msg_off) < 8 * m || CAP(msg_len) < 4 * m ||
+      (k_be && CAP(k_be) < 32 * m) || CAP(sig_out) < (size_t)sig_stride * m || CAP(sig_len_out) < 4 * m ||
+      (status && CAP(status) < m))
+    return CG_E_INVALID_ARGUMENT;
+  return cg_ecdsa_sign_batch(h > 0 ? CTX(h) : 0, (const cg_ecdsa_signer*)(intptr_t)signer, m, BUF(key_index), BUF(msg),
+                             CAP(msg), BUF(msg_off), BUF(msg_len), nonce_mode, BUF(k_be), BUF(sig_out),
+                             (size_t)sig_stride, BUF(sig_len_out), BUF(status));
 }
