@@ -212,11 +212,30 @@ CG_HD void ed25519_build_table(const ge_p3& P, Put&& put) {
   put(0, c);
   ge_p3_to_cached(c, P);
   put(1, c);
+  // Even multiples by doubling (4 squarings against the addition's 4 products), fed from
+  // the (X3 : Y3 : Z3) the cached conversion of k/2 P has anyway; odd ones as (k-1)P + P
+  // from the cached entry just made.  One rolled body (a doubling step, then an addition
+  // step) over k = 2, 3 | 6, 7 | 4, 5 | 8: 6P follows 3P at once, so only 2P's
+  // coordinates (qs) are kept across a step, then 4P's.  The formulas are complete: the
+  // same group elements as the add-only chain for every P.
+  static_assert(kATabEntries == 9, "the doubling order below covers k = 2..8");
   ge_p1p1 t;
-  CG_NOUNROLL for (int k = 2; k < kATabEntries; ++k) {  // (k-1)P + P, kept in cached form only
-    ge_add_cached(t, P, c, 0);
-    ge_p1p1_to_cached(c, t);
+  ge_p2 qa, qs, qe, qo;
+  qa.X = P.X;
+  qa.Y = P.Y;
+  qa.Z = P.Z;
+  qs = qa;
+  CG_NOUNROLL for (int i = 0; i < 4; ++i) {  // (i: wave-uniform)
+    const int k = i == 0 ? 2 : i == 1 ? 6 : i == 2 ? 4 : 8;
+    ge_p2_dbl<true>(t, qa);
+    ge_p1p1_to_cached(c, qe, t);
     put(k, c);
+    if (i == 3) break;
+    if (i != 1) qs = qe;  // 2P (for 4P), then 4P (for 8P)
+    ge_add_cached(t, P, c, 0);
+    ge_p1p1_to_cached(c, qo, t);
+    put(k + 1, c);
+    qa = i == 0 ? qo : qs;  // 3P, then 2P, then 4P
   }
 }
 

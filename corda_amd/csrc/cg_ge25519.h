@@ -62,13 +62,16 @@ CG_HD void ge_p3_to_cached(ge_cached& r, const ge_p3& p) {
 
 // p1p1 straight to cached: (Y3+X3, Y3-X3, Z3, 2d T3) with X3 = XT, Y3 = YZ,
 // Z3 = ZT, 2d T3 = (2d X) Y — five products in a triple and a pair.
-CG_HD void ge_p1p1_to_cached(ge_cached& r, const ge_p1p1& p) {
+// q = (X3 : Y3 : Z3), which the conversion has anyway: the input of a later doubling
+// (ed25519_build_table).
+CG_HD void ge_p1p1_to_cached(ge_cached& r, ge_p2& q, const ge_p1p1& p) {
   const fe d2 = CG_FE_D2;
-  fe x3, y3, dx;
-  fe_triple(x3, FeMulF{p.X, p.T}, y3, FeMulF{p.Z, p.Y}, dx, FeMulF{p.X, d2});
-  fe_pair(r.Z, FeMulF{p.Z, p.T}, r.T2d, FeMulF{dx, p.Y});
-  fe_add_p(r.YplusX, y3, x3);
-  fe_sub(r.YminusX, y3, x3);
+  fe dx;
+  fe_triple(q.X, FeMulF{p.X, p.T}, q.Y, FeMulF{p.Z, p.Y}, dx, FeMulF{p.X, d2});
+  fe_pair(q.Z, FeMulF{p.Z, p.T}, r.T2d, FeMulF{dx, p.Y});
+  r.Z = q.Z;
+  fe_add_p(r.YplusX, q.Y, q.X);
+  fe_sub(r.YminusX, q.Y, q.X);
 }
 
 // 2P: x = E/G, y = H/F with E = (X+Y)^2 - X^2 - Y^2, G = Y^2 - X^2,

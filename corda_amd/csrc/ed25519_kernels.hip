@@ -26,13 +26,16 @@
 //   msg_off[i] (u64, into the arena), msg_len[i]; scratch (`scap` = chunk):
 //   status[i] (verdict | digit count << 8 | R sign << 16), digits[w*scap+i]
 //   (24 words), and the per-signature tables entries 0..7 = k*(-A), 8..15 = k*R for
-//   k = 1..8 (cached points packed to 32 words = one 128-byte line)
+//   k = 1..8 (cached points packed to 32 words = one 128-byte line, cg_ed_table.h: each
+//   coordinate a 256-bit value equal to it mod p but not reduced — limbs carried into
+//   range once, never canonicalised; even k built by doubling, odd k by one addition)
 //   lane-contiguous: table[(i*17 + e)*32 + w] (one pad entry: CG_ED_TAB_PAD), 2,176 B per
 //   lane; a zero digit reads one shared identity entry.  (Round 3 measured a
 //   quad-major layout across lanes — each wave load one contiguous 1 KB run — slower:
 //   msm 7.11 -> 8.35 ms, points 2.47 -> 3.9 ms per 1 M, an entry's quads 16 MB apart.)
 #include "cg_ed25519.h"
 #include "cg_ed25519_sign.h"
+#include "cg_ed_table.h"
 #include "cg_kernels.h"
 
 using namespace cg;
@@ -48,12 +51,15 @@ namespace {
 #define CG_MSM_R_WAVES 2
 #endif
 
-// A table entry is its four coordinates as canonical 255-bit values (8 words each):
-// 128 B = one cache line per entry (round 3: against 160 B of limbs over two or three
-// lines, MSM -2 %); the points kernel canonicalises on store, the MSM unpacks
-// (floor-shaped limbs).  The lane tables keep k = 1..8 only (16 entries, 2 KB per lane);
+// A table entry is its four coordinates as 256-bit values (8 words each): 128 B = one
+// cache line per entry (round 3: against 160 B of limbs over two or three lines, MSM
+// -2 %).  The format lives in cg_ed_table.h (shared with the host tests): the points
+// kernels pack with one floor carry chain — no canonical form, the MSM never compares an
+// entry — and the MSM unpacks floor-shaped limbs (limb 9 up to 26 bits).  Every kernel
+// that stores or loads an entry goes through store_cached / unpack_entry below.
+// The lane tables keep k = 1..8 only (16 entries, 2 KB per lane);
 // a zero digit reads one shared identity entry (L1 / L2 resident) instead (+1 %).
-constexpr int kTabLimbs = 32;  // words per cached point: 4 fe x 8 packed
+constexpr int kTabLimbs = kEdEntryWords;  // words per cached point: 4 fe x 8 packed (cg_ed_table.h)
 constexpr int kSlotsPerPoint = kATabEntries - 1;
 // CG_ED_TAB_PAD: unused entries after a lane's table, so the lane stride is not a
 // power of two: at 16 entries = 2 KB every lane of a wave writes into the same L2
@@ -124,19 +130,14 @@ __global__ __launch_bounds__(256) CG_HASH_ATTR void cg_ed25519_hash(const uint32
   CG_UNROLL for (int w = 0; w < kDigitWords; ++w) digits[(size_t)w * scap + i] = dig[w];
 }
 
-// The shared identity entry (1, 1, 1, 0) in the table's entry format.
-__device__ __attribute__((aligned(128))) const int4 g_ident_entry[kTabLimbs / 4] = {
-    {1, 0, 0, 0}, {0, 0, 0, 0}, {1, 0, 0, 0}, {0, 0, 0, 0}, {1, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+// The shared identity entry (1, 1, 1, 0) in the table's entry format (cg_ed_table.h).
+__device__ __attribute__((aligned(128))) const int4 g_ident_entry[kTabLimbs / 4] = {CG_ED_IDENT_QUADS};
 
 CG_DEV void store_cached(int4* dst, const ge_cached& c) {
-  uint32_t w[4][8];
-  fe_tobytes(w[0], c.YplusX);
-  fe_tobytes(w[1], c.YminusX);
-  fe_tobytes(w[2], c.Z);
-  fe_tobytes(w[3], c.T2d);
-  CG_UNROLL for (int f = 0; f < 4; ++f)
-    CG_UNROLL for (int h = 0; h < 2; ++h)
-      dst[2 * f + h] = make_int4((int)w[f][4 * h], (int)w[f][4 * h + 1], (int)w[f][4 * h + 2], (int)w[f][4 * h + 3]);
+  uint32_t w[kTabLimbs];
+  ed_entry_pack(w, c);
+  CG_UNROLL for (int q = 0; q < kTabLimbs / 4; ++q)
+    dst[q] = make_int4((int)w[4 * q], (int)w[4 * q + 1], (int)w[4 * q + 2], (int)w[4 * q + 3]);
 }
 
 // A table entry in its storage form (the MSM fetches the A entry of a window before
@@ -146,19 +147,15 @@ struct RawEntry {
   int4 q[kTabLimbs / 4];
 };
 CG_DEV void unpack_entry(const RawEntry& r, ge_cached& c) {
-  uint32_t w[4][8];
-  CG_UNROLL for (int f = 0; f < 4; ++f)
-    CG_UNROLL for (int h = 0; h < 2; ++h) {
-      const int4 x = r.q[2 * f + h];
-      w[f][4 * h] = (uint32_t)x.x;
-      w[f][4 * h + 1] = (uint32_t)x.y;
-      w[f][4 * h + 2] = (uint32_t)x.z;
-      w[f][4 * h + 3] = (uint32_t)x.w;
-    }
-  fe_frombytes(c.YplusX, w[0]);
-  fe_frombytes(c.YminusX, w[1]);
-  fe_frombytes(c.Z, w[2]);
-  fe_frombytes(c.T2d, w[3]);
+  uint32_t w[kTabLimbs];
+  CG_UNROLL for (int q = 0; q < kTabLimbs / 4; ++q) {
+    const int4 x = r.q[q];
+    w[4 * q] = (uint32_t)x.x;
+    w[4 * q + 1] = (uint32_t)x.y;
+    w[4 * q + 2] = (uint32_t)x.z;
+    w[4 * q + 3] = (uint32_t)x.w;
+  }
+  ed_entry_unpack(c, w);
 }
 
 // Entry k (0..8) of point p (0: -A, 1: R; a per-signature table holding R only uses
